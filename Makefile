@@ -1,7 +1,7 @@
 SHELL=/bin/bash
 PY ?= python
 
-.PHONY: native test test-gpu bench bench-configs lint tsan asan coverage docker clean
+.PHONY: native test test-gpu bench bench-full bench-configs lint tsan asan coverage docker clean
 
 native:            ## build the C++ runtime in-tree
 	$(PY) -m beholder_amd.ops.build
@@ -14,6 +14,9 @@ test-gpu: native   ## box-tier tests (full-scale configs)
 
 bench: native      ## headline metric (driver contract)
 	$(PY) bench.py
+
+bench-full: native ## the headline and every other key of the bench line
+	$(PY) bench.py --full
 
 bench-configs: native  ## the five BASELINE.json configs
 	$(PY) -m beholder_amd bench all --out profiles/baseline_configs.json

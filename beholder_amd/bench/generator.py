@@ -67,23 +67,46 @@ class Workload:
         self._pc = codec_for(proto.load("api.TelemetryProgress"))
 
     def events(self, n: int) -> List[Tuple[int, bytes]]:
-        """``n`` (topic_id, payload) pairs."""
+        """``n`` (topic_id, payload) pairs.
+
+        The draws are ``rng.randrange(len(media))``, ``rng.randrange(len(STATUS_NAMES))``,
+        ``rng.random()``, ``rng.randint(0, 100)`` and ``rng.randrange(len(hosts))``, written out
+        as ``random.Random`` makes them (``getrandbits(k.bit_length())`` until the value is below
+        ``k``): the same stream at a third of the time, which is most of a bench run's set-up
+        (tests/test_bench_contract.py holds the stream to the plain calls)."""
         rng = self.rng
-        media = self.media
-        nm = len(media)
+        bits, rnd = rng.getrandbits, rng.random
+        ids = [m.id for m in self.media]
+        nm, ns, nh = len(ids), len(STATUS_NAMES), len(self.hosts)
+        if not nm or not nh:
+            raise ValueError("empty range for randrange()")  # as rng.randrange(0) says
+        km, ks, kh = nm.bit_length(), ns.bit_length(), nh.bit_length()
         out = []
+        add = out.append
         sc, pc = self._sc.encode, self._pc.encode
         hosts = self.hosts
+        unknown, progress = self.unknown_media_fraction, self.progress_fraction
         for _ in range(n):
-            if self.unknown_media_fraction and rng.random() < self.unknown_media_fraction:
-                mid = "missing-" + str(rng.getrandbits(32))
+            if unknown and rnd() < unknown:
+                mid = "missing-" + str(bits(32))
             else:
-                mid = media[rng.randrange(nm)].id
-            st = rng.randrange(len(STATUS_NAMES))
-            if rng.random() < self.progress_fraction:
-                out.append((PROGRESS_ID, pc((mid, st, rng.randint(0, 100), hosts[rng.randrange(len(hosts))]))))
+                r = bits(km)
+                while r >= nm:
+                    r = bits(km)
+                mid = ids[r]
+            st = bits(ks)
+            while st >= ns:
+                st = bits(ks)
+            if rnd() < progress:
+                p = bits(7)
+                while p > 100:
+                    p = bits(7)
+                h = bits(kh)
+                while h >= nh:
+                    h = bits(kh)
+                add((PROGRESS_ID, pc((mid, st, p, hosts[h]))))
             else:
-                out.append((STATUS_ID, sc((mid, st))))
+                add((STATUS_ID, sc((mid, st))))
         return out
 
     def framed(self, n: int) -> bytes:

@@ -25,8 +25,16 @@ then exactly ``K`` steps are timed, bracketed by a gloo barrier and ``torch.cuda
 on both sides (the service queues no device work: the reference has none).
 The elapsed time is the MAX over ranks.
 
-The same run also measures, as extra keys of the one JSON line (rank 0, outside the timed
-region):
+A plain run (``--gpus 1 --steps K --warmup W``) does only that: it sets up, warms up, times the
+K steps, writes its outputs where ``--dump-outputs DIR`` asks for them, and prints the line with the
+headline's own figures. Everything below runs only with ``--full``.
+
+``--dump-outputs DIR`` writes what the timed path produced in its last timed step (rank 0's consumer)
+as ``DIR/<name>.npy``, float64, see ``consumer_outputs``. The event streams depend on the arguments
+alone (``--seed``), so two builds run with the same arguments can be compared array for array.
+
+With ``--full`` the same run also measures, as extra keys of the one JSON line (rank 0, outside
+the timed region):
 
 * ``all_procs_*``: every CPU of the rank's share busy: ``--procs-per-rank`` consumer processes
   (competing consumers) on independent streams. This moves with the host's load.
@@ -48,11 +56,11 @@ region):
   ``tls_e2e_preconnect_*``: the same again with ``service.http.preconnect`` = 100 (sink
   connections and their handshakes made in init, ``_init_ms``; the default is 0, on demand).
 
-Order of the phases: (1) everything that starts child processes (config 1's CLI process, the TCP
-fakes, the all-process consumers); (2) the paced configs 2-4, in process, before HIP is touched;
-(3) the headline between two calibration runs, whose ``torch.cuda.synchronize()`` is the first
-HIP call of this process (a process that initialised the GPU must not start programs); (4) the
-soak (config 5).
+Order of the phases of a ``--full`` run: (1) everything that starts child processes (config 1's
+CLI process, the TCP fakes, the all-process consumers); (2) the paced configs 2-4, in process,
+before HIP is touched; (3) the headline between two calibration runs, whose
+``torch.cuda.synchronize()`` is the first HIP call of this process (a process that initialised
+the GPU must not start programs); (4) the soak (config 5).
 
 * ``plumbing_*``: BASELINE config 1, 100 events on the stdin of ``python -m beholder_amd run``
   with ``/metrics`` scraped before it exits.
@@ -97,12 +105,18 @@ def parse(argv=None):
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--events-per-step", type=int, default=65536, help="events per step per consumer process")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the all-process phase, BASELINE configs 1-5, "
+                         "the TCP / TLS production path, the shared-queue sweep and the calibrations "
+                         "(off: the headline alone)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step produced as DIR/<name>.npy (float64)")
     ap.add_argument("--procs-per-rank", type=int, default=0,
                     help="consumer processes per rank in the all-process phase (0 = min(16, CPUs per GPU slot - 1))")
     ap.add_argument("--all-procs-steps", type=int, default=10,
-                    help="timed steps of the all-process phase (0 = skip it)")
+                    help="--full: timed steps of the all-process phase (0 = skip it)")
     ap.add_argument("--no-extras", dest="extras", action="store_false",
-                    help="skip the rate_10k / soak / overload / TCP measurements")
+                    help="--full: skip the rate_10k / soak / overload / TCP measurements")
     ap.add_argument("--io-events", type=int, default=50000,
                     help="events of the preconnect and http_tcp measurements")
     ap.add_argument("--e2e-events", type=int, default=250000,
@@ -117,8 +131,9 @@ def parse(argv=None):
     ap.add_argument("--media", type=int, default=10000)
     ap.add_argument("--log-level", default="info")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--full-out", default=os.environ.get("BENCH_FULL_OUT", os.path.join(ROOT, "gpurun_out", "bench_full.json")),
-                    help="where the full record (every key of the run) is written; '' = nowhere")
+    ap.add_argument("--full-out", default=os.environ.get("BENCH_FULL_OUT"),
+                    help="where the full record (every key of the run) is written; '' = nowhere "
+                         "(default: bench_out/bench_full.json with --full, nowhere without)")
     ap.add_argument("--ordering", default="none", choices=["none", "per_media"])
     ap.add_argument("--pin", action="store_true",
                     help="pin each all-process consumer to its own CPU of the rank's affinity mask")
@@ -213,8 +228,64 @@ class _Dist:
             self.dist.destroy_process_group()
 
 
-async def run_consumer(a, seed: int, go, stop=None, *, steps: int = None, warmup: int = None) -> dict:
-    """One consumer: build the service, warm up, ``go()``, time ``steps`` steps, ``stop()``."""
+# the service's counters whose values are part of what a step produced (``--dump-outputs``)
+OUTPUT_COUNTERS = ("beholder_handler_errors_total", "beholder_progress_updates_total", "beholder_sink_requests_total",
+                   "beholder_trello_comments")
+
+
+def consumer_outputs(svc, settler, http, store, media, before) -> dict:
+    """What the consumer's last timed step produced, as float64 arrays (``--dump-outputs``):
+
+    * ``settled``: events acked, nacked, rejected and abandoned in that step;
+    * ``sink_requests``: sink requests made in that step;
+    * ``sink_request_tail_crc32``: CRC-32 of ``"METHOD url"`` of the last requests the stub kept, in order;
+    * ``counters`` / ``counters_last_step``: every series of OUTPUT_COUNTERS, sorted by name and label
+      values: its value after the step, and its growth over the step;
+    * ``store_status``: the status column of the media store after the step, in the media table's order.
+
+    ``before`` is :func:`_output_marks` taken when the step began."""
+    import zlib
+
+    import numpy as np
+    st0, http0, c0 = before
+    st1, c1 = settler.stats(), _counter_values(svc)
+    rows = store.snapshot()
+    names = sorted(c1)
+    return {
+        "settled": np.array([st1[k] - st0[k] for k in ("acked", "nacked", "rejected", "abandoned")], dtype=np.float64),
+        "sink_requests": np.array([http.count - http0], dtype=np.float64),
+        "sink_request_tail_crc32": np.array([zlib.crc32(f"{m} {u}".encode()) for m, u in http.calls],
+                                            dtype=np.float64),
+        "counters": np.array([c1[k] for k in names], dtype=np.float64),
+        "counters_last_step": np.array([c1[k] - c0.get(k, 0.0) for k in names], dtype=np.float64),
+        "store_status": np.array([rows[m.id].status for m in media], dtype=np.float64),
+    }
+
+
+def _counter_values(svc) -> dict:
+    out = {}
+    for name in OUTPUT_COUNTERS:
+        m = svc.registry.get(name)
+        for labels, v in (m.values() if m is not None else {}).items():
+            out[(name, *labels)] = float(v)
+    return out
+
+
+def _output_marks(svc, settler, http):
+    return dict(settler.stats()), http.count, _counter_values(svc)
+
+
+def dump_outputs(path: str, outputs: dict) -> None:
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(arr, dtype=np.float64))
+
+
+async def run_consumer(a, seed: int, go, stop=None, *, steps: int = None, warmup: int = None,
+                       outputs: bool = False) -> dict:
+    """One consumer: build the service, warm up, ``go()``, time ``steps`` steps, ``stop()``.
+    ``outputs``: also return what the last timed step produced (:func:`consumer_outputs`)."""
     from beholder_amd.bench.generator import Workload, bench_config
     from beholder_amd.config import Config
     from beholder_amd.service import Service
@@ -238,7 +309,8 @@ async def run_consumer(a, seed: int, go, stop=None, *, steps: int = None, warmup
     cfg = Config.from_dict(cfg_d)
     log_sink = open(os.devnull, "w", buffering=1 << 16)
     http = RecordingHttpClient(keep=16, stub=STUB)
-    svc = Service(cfg, source=FdSource(fd=rfd, batch=512), store=MemoryStore(w.media), http=http,
+    store = MemoryStore(w.media)
+    svc = Service(cfg, source=FdSource(fd=rfd, batch=512), store=store, http=http,
                   logger=Logger(stream=log_sink, level=a.log_level), serve_metrics=False)
     await svc.init()
     run_task = asyncio.ensure_future(svc.run())
@@ -274,6 +346,7 @@ async def run_consumer(a, seed: int, go, stop=None, *, steps: int = None, warmup
     t0 = 0.0
     ru0 = None
     rq0 = pq0 = rq1 = pq1 = rqg = None
+    marks = None
     for i in range(total_steps):
         if i == warmup:
             settler.reset_latency()
@@ -285,6 +358,8 @@ async def run_consumer(a, seed: int, go, stop=None, *, steps: int = None, warmup
             # thread of the process alive across them (the native reader thread, HIP's runtime
             # threads started by go()'s synchronize); the pump threads report their own
             rq0, pq0 = thread_run_delay_ns(), proc_run_delay_ns()
+        if outputs and steps and i == total_steps - 1:
+            marks = _output_marks(svc, settler, http)
         th = write_step(i, i >= warmup)
         await wait_settled((i + 1) * E)
         th.join()
@@ -299,6 +374,7 @@ async def run_consumer(a, seed: int, go, stop=None, *, steps: int = None, warmup
     log_sink.close()
     st = svc.stats()
     return {
+        **({"outputs": consumer_outputs(svc, settler, http, store, w.media, marks)} if marks is not None else {}),
         "elapsed": elapsed,
         "events": E * steps,
         "handle_hist": settler.handle_latency.to_bytes(),
@@ -328,7 +404,8 @@ def run_solo(a, dist: _Dist, dev: _Device) -> dict:
         dev.sync()
         dist.barrier()
 
-    res = asyncio.run(run_consumer(a, a.seed + 7919 * dist.rank, go, dev.sync))
+    res = asyncio.run(run_consumer(a, a.seed + 7919 * dist.rank, go, dev.sync,
+                                   outputs=bool(a.dump_outputs) and dist.rank == 0))
     res["procs"] = 1
     return res
 
@@ -806,6 +883,10 @@ NOTES = ("CPU event-consumer workload (the reference has no device compute; see 
          "plumbing_* = BASELINE config 1 through `python -m beholder_amd run --source stdin`, "
          "/metrics scraped before exit")
 
+PLAIN_NOTES = ("CPU event-consumer workload (the reference has no device compute; see docs/DESIGN.md). "
+               "value = one consumer process per rank; the headline alone: --full adds the all-process phase, "
+               "BASELINE configs 1-5, the TCP / TLS production path and the calibrations")
+
 # The driver keeps the tail of stdout (its `tail` field: the last ~2,000 characters; its
 # `stdout_tail`: the last ~8,000), so the one JSON line is built for that:
 # the contract keys first, then diagnostics while the line stays within LINE_BUDGET characters,
@@ -918,23 +999,28 @@ def main(argv=None) -> int:
     from beholder_amd.utils.hostinfo import (cgroup_cpu_stat, cgroup_delta, host_busy_pct, host_cpu_times,
                                              thread_run_delay_ns)
 
+    # everything beside the headline runs with --full alone
+    more = a.full and a.extras
+    full_out = a.full_out if a.full_out is not None else (os.path.join(ROOT, "bench_out", "bench_full.json")
+                                                          if a.full else "")
+
     # 1. phases that start child processes (before any HIP call in this process)
-    if a.extras and dist.rank == 0:
+    if more and dist.rank == 0:
         extras.update(_phase("io_extras", io_extras, a))
     dist.barrier()
     allp = None
-    if a.all_procs_steps > 0 and procs > 1:
+    if a.full and a.all_procs_steps > 0 and procs > 1:
         allp = run_procs(a, dist, procs, a.all_procs_steps)
     allp_elapsed = dist.max(allp["elapsed"] if allp else 0.0)
     allp_events = sum(dist.gather(allp["events"] if allp else 0))
 
     # 2. paced BASELINE configs 2-4 (in process, before HIP is initialised)
-    if a.extras and dist.rank == 0:
+    if more and dist.rank == 0:
         extras.update(_phase("paced_extras", paced_extras, a))
     dist.barrier()
 
-    # 3. the headline: one consumer per rank, K timed steps, between two calibration runs
-    calib0 = calibrate()
+    # 3. the headline: one consumer per rank, K timed steps (--full: between two calibration runs)
+    calib0 = calibrate() if a.full else None
     cg0 = cgroup_cpu_stat()
     h0 = host_cpu_times()
     gc.collect()
@@ -944,7 +1030,7 @@ def main(argv=None) -> int:
     dist.barrier()
     cg1 = cgroup_cpu_stat()
     h1 = host_cpu_times()
-    calib1 = calibrate()
+    calib1 = calibrate() if a.full else None
     elapsed = dist.max(res["elapsed"])
     parts = dist.gather({k: res[k] for k in ("handle_hist", "ingest_hist", "http_calls", "errors", "abandoned",
                                              "events", "cpu_s", "nivcsw", "minflt", "majflt", "timed_run_delay_ms",
@@ -956,7 +1042,7 @@ def main(argv=None) -> int:
     run_delays = dist.gather((rq1 - rq0) / 1e6 if rq0 is not None and rq1 is not None else None)
 
     # 4. BASELINE config 5 (no child processes: HIP may be initialised now)
-    if a.extras and dist.rank == 0:
+    if more and dist.rank == 0:
         extras.update(_phase("soak_extras", soak_extras, a))
     dist.barrier()
 
@@ -968,16 +1054,19 @@ def main(argv=None) -> int:
         total_events = sum(p["events"] for p in parts)
         value = total_events / elapsed
         cal = {}
-        for k in CALIB_REF:  # the slowest rank's worse side of the headline
+        for k in CALIB_REF if a.full else ():  # the slowest rank's worse side of the headline
             cal[k] = max(max(c0[k], c1[k]) for c0, c1 in calibs)
             cal[k + "_before"] = calib0[k]
             cal[k + "_after"] = calib1[k]
-        ref = CALIB_REF["calib_ns"]
-        cal.update({"calib_ref": CALIB_REF,
-                    # what a box with the reference box's core speed (the C loop) would give
-                    "value_calibrated": round(value * cal["calib_ns"] / ref, 1) if ref else None,
-                    "headline_host_cpu_busy_pct": host_busy_pct(h0, h1),
+        if a.full:
+            ref = CALIB_REF["calib_ns"]
+            # what a box with the reference box's core speed (the C loop) would give
+            cal.update({"calib_ref": CALIB_REF,
+                        "value_calibrated": round(value * cal["calib_ns"] / ref, 1) if ref else None})
+        cal.update({"headline_host_cpu_busy_pct": host_busy_pct(h0, h1),
                     **_cg("headline", cgroup_delta(cg0, cg1))})
+        allp_keys = {"all_procs_per_rank": procs if allp is not None else 0,
+                     "all_procs_events_per_sec": round(allp_events / allp_elapsed, 1) if allp_elapsed else None}
         full = {
             "metric": BASELINE_METRIC,
             "value": round(value, 1),
@@ -1016,16 +1105,17 @@ def main(argv=None) -> int:
             **cal,
             "http_requests": sum(p["http_calls"] for p in parts),
             "handler_errors": sum(p["errors"] for p in parts),
-            "all_procs_per_rank": procs if allp is not None else 0,
-            "all_procs_events_per_sec": round(allp_events / allp_elapsed, 1) if allp_elapsed else None,
+            **(allp_keys if a.full else {}),
             "cpus_available": available_cpus(),
             "cpu_share": cpu_share(),
             "gpus_on_node": gpus_on_node(),
             **extras,
-            "notes": NOTES,
+            "notes": NOTES if a.full else PLAIN_NOTES,
         }
         full = _finite(full)
-        full_path = _write_full(a.full_out, full)
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, res["outputs"])
+        full_path = _write_full(full_out, full)
         out = compact_line(full, full_path)
         print(json.dumps(out, allow_nan=False), flush=True)
     dist.close()

@@ -93,7 +93,7 @@ def run_ours(a) -> dict:
     if a.procs == 1:
         cmd += ["--procs-per-rank", "1", "--all-procs-steps", "0", "--seed", str(a.seed)]
     else:
-        cmd += ["--procs-per-rank", str(a.procs), "--all-procs-steps", str(a.steps), "--seed", str(a.seed - 1)]
+        cmd += ["--full", "--procs-per-rank", str(a.procs), "--all-procs-steps", str(a.steps), "--seed", str(a.seed - 1)]
     out = json.loads(subprocess.run(cmd, check=True, capture_output=True, text=True).stdout.strip().splitlines()[-1])
     if a.procs > 1:
         out["value"] = out["all_procs_events_per_sec"]

@@ -6,6 +6,6 @@ out=gpurun_out/${OUT:-box_r4_bench}
 mkdir -p "$out"
 runs=${RUNS:-2}
 for i in $(seq 1 "$runs"); do
-  timeout -k 10 300 python3 bench.py --gpus 1 --steps 20 --warmup 5 $ARGS > "$out/bench_$i.json" 2> "$out/bench_$i.err" || exit $?
+  timeout -k 10 300 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 $ARGS > "$out/bench_$i.json" 2> "$out/bench_$i.err" || exit $?
   echo "run $i done: $(head -c 200 "$out/bench_$i.json")"
 done

@@ -8,7 +8,7 @@ out=gpurun_out/${OUT:-r5_inline_ab}
 mkdir -p "$out"
 for i in $(seq 1 "${RUNS:-3}"); do
   for arm in fresh full; do
-    if [ "$arm" = fresh ]; then extra="--no-extras"; else extra=""; fi
+    if [ "$arm" = fresh ]; then extra="--no-extras"; else extra="--full"; fi
     timeout -k 10 300 python bench.py --steps 20 --warmup 5 $extra --full-out "$out/full_$arm$i.json" > "$out/line.json" 2>> "$out/err.log" || exit 1
     python -c "import json; d=json.load(open('$out/full_$arm$i.json')); print(json.dumps({'arm': '$arm', 'pair': $i, 'value': d['value'], 'cpu_us': d['cpu_us_per_event'], 'p50': d['p50_handle_latency_us'], 'calib_ns': d['calib_ns'], 'minflt': d.get('headline_minflt')}))" >> "$out/runs.jsonl"
   done

@@ -9,7 +9,7 @@ run() {  # run <n> <port> <tag> [bench args...]
   local n=$1 port=$2 tag=$3
   shift 3
   timeout -k 10 420 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$n" --master-addr 127.0.0.1 \
-    --master-port "$port" bench.py --gpus "$n" --steps 20 --warmup 5 "$@" > "$out/$tag.json" 2> "$out/$tag.err"
+    --master-port "$port" bench.py --full --gpus "$n" --steps 20 --warmup 5 "$@" > "$out/$tag.json" 2> "$out/$tag.err"
 }
 run 2 29611 n2 --full-out "$out/n2_full.json" &&
 run 4 29612 n4 --no-extras --full-out "$out/n4_full.json"

@@ -10,7 +10,7 @@ root=$PWD
 for i in $(seq 1 "${RUNS:-3}"); do
   for arm in new old; do
     if [ "$arm" = old ]; then dir=$root/ab_old; else dir=$root; fi
-    (cd "$dir" && timeout -k 10 240 python bench.py --gpus 1 --steps 20 --warmup 5 --full-out "$root/$out/${arm}_$i.json" > "$root/$out/${arm}_$i.line" 2> "$root/$out/${arm}_$i.err") || exit 1
+    (cd "$dir" && timeout -k 10 240 python bench.py --full --gpus 1 --steps 20 --warmup 5 --full-out "$root/$out/${arm}_$i.json" > "$root/$out/${arm}_$i.line" 2> "$root/$out/${arm}_$i.err") || exit 1
     python -c "
 import json
 d = json.load(open('$out/${arm}_$i.json'))

@@ -26,12 +26,22 @@ What the stand-ins assume is listed in their headers. The ones that touch this c
 ``NOT_FOUND`` and ignores ``updateStatus`` of one; ``trello@0.9.1`` resolves on any HTTP status;
 ``request-promise`` rejects non-2xx with ``StatusCodeError``.
 
+The reference's result for every scenario the suite replays is also kept, as the reference gave
+it, under ``tests/golden/reference_oracle/`` (one gzipped JSON document per scenario, named by
+the scenario's hash). Where Node and the reference checkout are present :func:`run_node` runs the
+reference and holds a kept result to what it just gave; where they are not, it answers from the
+kept result, so the gate runs everywhere. ``BEHOLDER_ORACLE_RECORD=1`` (with Node and the
+checkout) writes the results of the scenarios a run replays: run the suite once with it after
+changing a scenario or a stand-in.
+
 Run by ``tests/test_reference_oracle.py``; by hand:
 ``python tests/reference_oracle.py --seeds 10 --events 600``.
 """
 from __future__ import annotations
 
 import asyncio
+import gzip
+import hashlib
 import json
 import os
 import random
@@ -69,8 +79,35 @@ _S = codec_for(proto.load("api.TelemetryStatus"))
 _P = codec_for(proto.load("api.TelemetryProgress"))
 
 
-def available() -> bool:
+GOLDEN = os.path.join(HERE, "golden", "reference_oracle")
+
+
+def live() -> bool:
+    """Node and the reference checkout are here: :func:`run_node` runs the reference itself."""
     return NODE is not None and os.path.exists(REFERENCE_INDEX)
+
+
+def available() -> bool:
+    return live() or os.path.isdir(GOLDEN)
+
+
+def _golden_path(sc: dict) -> str:
+    key = hashlib.sha256(json.dumps(sc, sort_keys=True).encode()).hexdigest()[:20]
+    return os.path.join(GOLDEN, key + ".json.gz")
+
+
+def _recorded(sc: dict) -> Optional[dict]:
+    try:
+        with gzip.open(_golden_path(sc), "rt", encoding="utf-8") as f:
+            return json.load(f)
+    except FileNotFoundError:
+        return None
+
+
+def _record(sc: dict, out: dict) -> None:
+    os.makedirs(GOLDEN, exist_ok=True)
+    with open(_golden_path(sc), "wb") as raw, gzip.GzipFile(fileobj=raw, mode="wb", mtime=0) as f:
+        f.write(json.dumps(out, separators=(",", ":"), ensure_ascii=False).encode("utf-8"))
 
 
 # ---------------------------------------------------------------------------------- scenarios ---
@@ -250,7 +287,14 @@ def bench_scenario(n_events: int, seed: int = 0) -> dict:
 
 # ------------------------------------------------------------------------------------- runners ---
 def run_node(sc: dict, timeout: float = 120.0) -> dict:
-    """The reference's own index.js on Node, under the stand-ins (oracle.js)."""
+    """The reference's own index.js on Node, under the stand-ins (oracle.js); without Node or
+    the checkout, what it gave for this scenario when the result was recorded."""
+    if not live():
+        out = _recorded(sc)
+        if out is None:
+            raise RuntimeError(f"no recorded reference result for this scenario (seed {sc.get('seed')}, mode "
+                               f"{sc.get('mode')}, {len(sc['events'])} events) and no Node / reference checkout to run it")
+        return out
     env = dict(os.environ, NODE_PATH=STUBS)
     env.pop("NO_TRELLO", None)
     if sc.get("noTrello"):
@@ -265,7 +309,15 @@ def run_node(sc: dict, timeout: float = 120.0) -> dict:
         os.unlink(path)
     if r.returncode != 0:
         raise RuntimeError(f"oracle.js failed ({r.returncode}): {r.stderr[-2000:]}")
-    return json.loads(r.stdout)
+    out = json.loads(r.stdout)
+    if os.environ.get("BEHOLDER_ORACLE_RECORD") == "1":
+        _record(sc, out)
+    else:
+        kept = _recorded(sc)
+        if kept is not None and kept != out:
+            raise RuntimeError(f"the recorded reference result {_golden_path(sc)} is stale: the reference now gives "
+                               "another (record again with BEHOLDER_ORACLE_RECORD=1)")
+    return out
 
 
 def _counter_hashes(counter, label_names) -> list:

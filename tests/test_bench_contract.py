@@ -59,7 +59,7 @@ def _last_json(stdout: str) -> dict:
 
 def test_bench_single_rank_contract(tmp_path):
     full_path = str(tmp_path / "full.json")
-    r = subprocess.run([sys.executable, "bench.py", *SMALL, "--procs-per-rank", "2", "--all-procs-steps", "1",
+    r = subprocess.run([sys.executable, "bench.py", "--full", *SMALL, "--procs-per-rank", "2", "--all-procs-steps", "1",
                         "--io-events", "2000", "--e2e-events", "4000", "--soak-events", "20000",
                         "--shared-queue-events", "3000", "--e2e-repeats", "2", "--e2e-paced-scale", "0.1",
                         "--full-out", full_path],
@@ -144,7 +144,7 @@ def test_bench_two_ranks_gloo():
     pytest.importorskip("torch")  # torch.distributed.run launches the ranks
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", "29561", "bench.py", "--gpus", "2",
-                        *SMALL, "--procs-per-rank", "2", "--all-procs-steps", "1", "--no-extras"],
+                        "--full", *SMALL, "--procs-per-rank", "2", "--all-procs-steps", "1", "--no-extras"],
                        cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     out = _last_json(r.stdout)
@@ -211,7 +211,7 @@ def test_no_hip_before_child_processes(monkeypatch, capsys):
     monkeypatch.setattr(bench._Device, "sync", spy_sync)
     monkeypatch.setattr(harness, "_spawn", spy_spawn)
     monkeypatch.setattr(bench, "run_procs", spy_procs)
-    assert bench.main([*SMALL, "--procs-per-rank", "2", "--all-procs-steps", "1", "--io-events", "1000",
+    assert bench.main(["--full", *SMALL, "--procs-per-rank", "2", "--all-procs-steps", "1", "--io-events", "1000",
                        "--e2e-events", "1000", "--soak-events", "5000", "--shared-queue-events", "0",
                        "--e2e-paced-scale", "0"]) == 0
     out = _last_json(capsys.readouterr().out)
@@ -258,3 +258,107 @@ def test_compact_line_keeps_decision_keys_last_and_fits():
     assert tail_keys[-1] == "value"
     start = line.index(f'"{bench.TAIL_KEYS[0]}"')
     assert len(line) - start <= bench.TAIL_BUDGET, len(line) - start
+
+
+# what only --full measures: none of it may appear on (or run for) a plain line
+FULL_ONLY = ("all_procs_events_per_sec", "all_procs_per_rank", "calib_ns", "value_calibrated", "plumbing_rc",
+             "rate_1k_acked", "rate_10k_acked", "burst_offered", "soak_events", "tcp_e2e_events_per_sec",
+             "tls_e2e_events_per_sec", "shared_queue_events_per_sec", "http_tcp_h1_events_per_sec")
+PLAIN = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--events-per-step", "4096", "--media", "500"]
+OUTPUT_NAMES = {"settled", "sink_requests", "sink_request_tail_crc32", "counters", "counters_last_step",
+                "store_status"}
+
+
+def _load_outputs(d) -> dict:
+    import numpy as np
+    return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+
+
+def test_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path, monkeypatch, capsys):
+    """`bench.py --gpus 1 --steps K --warmup W`: the headline and nothing else (no child process,
+    no calibration, no full record), K timed steps, and with --dump-outputs the last step's outputs
+    as float64 arrays that a second run with the same arguments reproduces exactly."""
+    import numpy as np
+
+    import bench
+    from beholder_amd.bench import harness
+    a_dir, b_dir = str(tmp_path / "a"), str(tmp_path / "b")
+    r = subprocess.run([sys.executable, "bench.py", *PLAIN, "--dump-outputs", a_dir],
+                       cwd=ROOT, capture_output=True, text=True, timeout=300,
+                       env={k: v for k, v in os.environ.items() if k != "BENCH_FULL_OUT"})
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = _last_json(r.stdout)
+    assert REQUIRED <= set(out) and out["steps"] == 3 and out["warmup"] == 1 and out["n_gpus"] == 1
+    assert out["metric"] == bench.BASELINE_METRIC and out["unit"] == "events/s" and out["higher_is_better"] is True
+    assert out["value"] == pytest.approx(4096 * 3 / (out["ms_per_step"] * 3 / 1000), rel=0.01)
+    assert out["handler_errors"] == 0 and out["full_record"]["path"] is None
+    assert not [k for k in out if k in FULL_ONLY or k.startswith(("tcp_e2e_", "tls_e2e_", "rate_", "soak_", "calib_"))]
+
+    # the same arguments in this process: nothing but the headline runs, and the outputs are the same
+    def never(*a, **k):
+        raise AssertionError("a plain run starts nothing beside its headline")
+    for name in ("io_extras", "paced_extras", "soak_extras", "run_procs", "calibrate"):
+        monkeypatch.setattr(bench, name, never)
+    monkeypatch.setattr(harness, "_spawn", never)
+    # (the device bracket is left out here: this process goes on to start programs in later tests)
+    monkeypatch.setattr(bench._Device, "sync", lambda self: None)
+    monkeypatch.delenv("BENCH_FULL_OUT", raising=False)
+    assert bench.main([*PLAIN, "--dump-outputs", b_dir]) == 0
+    again = _last_json(capsys.readouterr().out)
+    assert again["full_record"]["path"] is None
+    a, b = _load_outputs(a_dir), _load_outputs(b_dir)
+    assert set(a) == set(b) == OUTPUT_NAMES
+    assert all(v.dtype == np.float64 for v in a.values()) and sum(v.nbytes for v in a.values()) < 64 << 20
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    # the last step alone: its 4096 events settled, each progress update counted once
+    assert a["settled"].sum() == 4096 and a["settled"][0] > 0
+    assert a["store_status"].shape == (500,) and 0 < a["sink_requests"][0] <= 3 * 4096
+    assert len(a["sink_request_tail_crc32"]) == 16
+    assert (a["counters_last_step"] >= 0).all() and (a["counters_last_step"] <= a["counters"]).all()
+    assert 0 < a["counters_last_step"].sum() < a["counters"].sum()
+
+
+def test_dumped_outputs_follow_the_seed(tmp_path, monkeypatch, capsys):
+    """Another seed is another event stream: the dumped outputs differ (they are the run's, not constants)."""
+    import numpy as np
+
+    import bench
+    monkeypatch.setattr(bench._Device, "sync", lambda self: None)  # no HIP in the test process, as above
+    dirs = [str(tmp_path / s) for s in ("s0", "s1")]
+    for d, seed in zip(dirs, ("0", "1")):
+        assert bench.main([*PLAIN, "--steps", "1", "--warmup", "0", "--seed", seed, "--dump-outputs", d]) == 0
+    capsys.readouterr()
+    a, b = _load_outputs(dirs[0]), _load_outputs(dirs[1])
+    assert not np.array_equal(a["sink_request_tail_crc32"], b["sink_request_tail_crc32"])
+    assert not np.array_equal(a["store_status"], b["store_status"])
+
+
+def test_workload_stream_is_the_plain_random_calls():
+    """Workload.events writes its draws out by hand (bench set-up time); the stream is the one the
+    plain ``random.Random`` calls give, unknown media included."""
+    import random
+
+    from beholder_amd.bench.generator import STATUS_NAMES, Workload
+    from beholder_amd.topics import PROGRESS_ID, STATUS_ID
+
+    def plain(w, rng, n):
+        out = []
+        for _ in range(n):
+            if w.unknown_media_fraction and rng.random() < w.unknown_media_fraction:
+                mid = "missing-" + str(rng.getrandbits(32))
+            else:
+                mid = w.media[rng.randrange(len(w.media))].id
+            st = rng.randrange(len(STATUS_NAMES))
+            if rng.random() < w.progress_fraction:
+                out.append((PROGRESS_ID, w._pc.encode((mid, st, rng.randint(0, 100),
+                                                       w.hosts[rng.randrange(len(w.hosts))]))))
+            else:
+                out.append((STATUS_ID, w._sc.encode((mid, st))))
+        return out
+    for kw in ({"n_media": 500}, {"n_media": 1024, "unknown_media_fraction": 0.05}, {"n_media": 3, "hosts": ("a", "b", "c")},
+               {"n_media": 1, "hosts": ("a",), "progress_fraction": 0.5}):
+        w = Workload(seed=5, **kw)
+        rng = random.Random()
+        rng.setstate(w.rng.getstate())
+        assert w.events(3000) + w.events(10) == plain(w, rng, 3010), kw

@@ -82,7 +82,7 @@ def test_compiled_handlers_match_python_on_the_box():
 
 
 def test_bench_single_rank_full_path():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "5", "--warmup", "1",
                           "--e2e-repeats", "1", "--e2e-events", "50000", "--shared-queue-events", "20000",
                           "--full-out", ""],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
@@ -115,7 +115,8 @@ def test_bench_two_ranks_torchrun_on_box():
     """The driver's multi-GPU launch path (torch.distributed.run, gloo barriers, MAX over ranks)."""
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", "29571", os.path.join(ROOT, "bench.py"),
-                          "--gpus", "2", "--steps", "3", "--warmup", "1", "--procs-per-rank", "2", "--no-extras"],
+                          "--gpus", "2", "--full", "--steps", "3", "--warmup", "1", "--procs-per-rank", "2",
+                          "--no-extras"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     r = json.loads([x for x in out.stdout.splitlines() if x.startswith("{")][-1])

@@ -91,6 +91,8 @@ def _tree(tmp_path, mutation=None):
     os.makedirs(dst / "tests")
     for f in ("reference_oracle.py", "helpers.py", "conftest.py", "test_handlers.py", "pg_fake.py"):
         shutil.copy(os.path.join(HERE, f), dst / "tests" / f)
+    if os.path.isdir(ro.GOLDEN):  # the reference's recorded results, for where it cannot run
+        shutil.copytree(ro.GOLDEN, dst / "tests" / "golden" / "reference_oracle")
     if mutation:
         path, old, new, _ = MUTATIONS[mutation]
         with open(dst / path) as f:
