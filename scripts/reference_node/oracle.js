@@ -17,7 +17,8 @@
 // scenario.json: {config, media: [{id,name,creator,creatorId,metadataId,status}],
 //   events: [["status"|"progress", hexBody]], faults: [{method, prefix, status|null, message, body}],
 //   positionalArgs: "append"|"drop", notFound: "media {id} not found", logLevel: "info",
-//   races: {mediaId: status} (the status another writer leaves in the row after each updateStatus)}
+//   races: {mediaId: status} (the status another writer leaves in the row after each updateStatus),
+//   storeFaults: [{op: "updateStatus"|"getByID", id, message}] (that store call rejects with that text)}
 //   concurrent: {cap, script} (scenario mode "concurrent", below)
 // NO_TRELLO comes from the environment, as in the reference (index.js:70).
 // Events are delivered one at a time and each listener's promise is awaited before the next
@@ -64,6 +65,7 @@ const h = global.__beholderHarness = {
   positionalArgs: sc.positionalArgs || 'append',
   notFound: sc.notFound,
   races: sc.races || {},
+  storeFaults: sc.storeFaults || [],
   logSink: {
     write (s) {
       for (const line of s.split('\n')) {

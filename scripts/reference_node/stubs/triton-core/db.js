@@ -14,6 +14,15 @@ class Storage {
     this.media = h.media
     this.notFound = h.notFound || 'media {id} not found'
     this.races = h.races || {}
+    this.storeFaults = h.storeFaults || []
+  }
+
+  // scenario key "storeFaults": [{op, id, message}] rejects that call for that row with that
+  // text, before it touches the table (a failed UPDATE leaves the row as it was)
+  fault (op, mediaId) {
+    for (const f of this.storeFaults) {
+      if (f.op === op && f.id === mediaId) throw new Error(f.message)
+    }
   }
 
   // Mode "concurrent" (oracle.js): each call first waits on the harness's gate; the UPDATE
@@ -21,6 +30,7 @@ class Storage {
   // query returns a fresh row object: a row read before another event's UPDATE keeps its status.
   async updateStatus (mediaId, status) {
     if (this.h.gate) await this.h.gate('update')
+    this.fault('updateStatus', mediaId)
     const m = this.media.get(mediaId)
     if (m) m.status = status
     // scenario mode "reread": another writer's UPDATE of the same row lands between this
@@ -31,6 +41,7 @@ class Storage {
 
   async getByID (mediaId) {
     if (this.h.gate) await this.h.gate('get')
+    this.fault('getByID', mediaId)
     const m = this.media.get(mediaId)
     if (!m) throw new Error(this.notFound.split('{id}').join(mediaId))
     return Object.assign({}, m)

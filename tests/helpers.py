@@ -63,7 +63,8 @@ SUSPEND = False
 def suspending(base):
     """``base`` (a MemoryStore class) whose every access yields to the loop once before it runs
     (a network store's shape). Its synchronous accessors are hidden from the handlers, so
-    they await the coroutines."""
+    they await the coroutines: also where ``base`` overrides one (MemoryStore hides an accessor
+    only where no subclass has its own)."""
     class Suspending(base):
         async def update_status(self, media_id, status):
             await asyncio.sleep(0)
@@ -72,6 +73,7 @@ def suspending(base):
         async def get_by_id(self, media_id):
             await asyncio.sleep(0)
             return base.get_by_id_nowait(self, media_id)
+    Suspending.update_status_nowait = Suspending.get_by_id_nowait = None
     Suspending.__name__ = Suspending.__qualname__ = "Suspending" + base.__name__
     return Suspending
 

@@ -14,12 +14,24 @@ A scenario (:func:`make_scenario`) is a seeded random config, media table, sink-
 event stream. The streams are built to reach every branch of index.js:50-155, malformed bodies
 included (truncated fields, wrong wire types, unknown fields and groups, invalid UTF-8, field
 number 0). Modes: ``base``, ``no_trello`` (NO_TRELLO set, index.js:70), ``faults`` (transport
-errors and non-2xx answers from Trello, Telegram and Emby, index.js:92-122), ``drop``
-(``positional_args: drop``, pino@5's exact message text, quirk Q11) and ``reread`` (another writer
-updates chosen rows between the listener's ``updateStatus`` and its ``getByID``, index.js:68,76:
+errors and non-2xx answers from Trello, Telegram and Emby, index.js:92-122, and store errors;
+below), ``drop`` (``positional_args: drop``, pino@5's exact message text, quirk Q11) and
+``reread`` (another writer updates chosen rows between the listener's ``updateStatus`` and its
+``getByID``, index.js:68,76:
 the re-read status differs from the message's, so a handler that keys the hooks off the message's
 status instead of the row's, quirk Q3 at index.js:94, or the list off the row's instead of the
 message's, index.js:74-80, diverges from the reference).
+
+Mode ``faults`` fails every awaited call of index.js on every seed, ahead of its random pool of
+sink faults (the first match answers): Telegram for the rows named "Cowboy Bebop" (row ``m2``), the
+comment POST on ``card1`` (row ``m1``), the card-move PUT of row ``m3``'s card, every Emby GET
+(row ``m6`` always reaches it after a Telegram success), ``updateStatus`` of row ``m4`` and
+``getByID`` of row ``m5`` (scenario key ``storeFaults``, present in this mode only: the Node store
+stand-in and :class:`FaultyStore` fail the same call with the same text).
+:func:`forced_failure_coverage` counts the events that hit each. Over real sockets
+(:func:`for_sockets`) the forced failures stay failures: the sink server drops the connection
+without answering, the Postgres server sends an ErrorResponse, and the compared texts are the
+production clients' own.
 
 What the stand-ins assume is listed in their headers. The ones that touch this comparison:
 ``triton-core/db`` (not vendored) rejects ``getByID`` of an unknown id with the text in
@@ -72,6 +84,11 @@ NOT_FOUND = "media {id} not found"  # beholder_amd.store.base.MediaNotFound's te
 # sendMessage for a row named "Cowboy Bebop" (query order chat_id, text, parse_mode; RFC 3986)
 TELEGRAM_FAULT_PREFIX = ("https://api.telegram.org/bot123:TG/sendMessage?chat_id=-1001&text="
                          "%2ANew%20Anime%3A%2A%20Cowboy%20Bebop")
+# mode "faults": the card whose move always fails (row m3), and the store's forced error texts
+FORCED_MOVE_CARD = "card-m3"
+UPDATE_FAULT = "deadlock detected"                             # updateStatus of row m4
+GET_FAULT = "canceling statement due to statement timeout"     # getByID of row m5
+PG_FAULT_SQLSTATE = "XX000"  # what tests/pg_fake.py sends with an error it has no code for
 MODES = ("base", "no_trello", "faults", "drop", "reread", "concurrent")
 CONCURRENT_CAP = 4  # deliveries in flight at once in mode "concurrent"
 
@@ -193,6 +210,7 @@ def make_scenario(seed: int, n_events: int = 520, mode: str = "base") -> dict:
         config["instance"]["emby"] = {"enabled": rng.choice([True, True, False]),
                                       "host": rng.choice(["http://emby:8096", "https://e.example/x"])}
     faults: List[dict] = []
+    store_faults: List[dict] = []
     if mode == "faults":  # both hooks on, so a Telegram failure visibly skips Emby (Q4)
         config["keys"]["telegram"] = {"token": "123:TG"}
         config["keys"]["emby"] = {"token": "EMBYKEY"}
@@ -205,18 +223,34 @@ def make_scenario(seed: int, n_events: int = 520, mode: str = "base") -> dict:
         # others, so a handler that runs Emby after a failed Telegram call diverges, Q4,
         # index.js:92-122) and a failing comment POST on card "card1" (its counter must not count,
         # index.js:53-57, and the progress handler still acks, Q7)
+        # and, forced on every seed as well (each awaited call of index.js fails somewhere): the
+        # card move of row m3 (index.js:83-86: un-acked, Q1), every Emby refresh (index.js:112,
+        # after a Telegram success: warned and acked; the URL names no media, so Emby succeeds only
+        # in the other modes), updateStatus of row m4 (index.js:68) and getByID of row m5
+        # (index.js:76: un-acked; index.js:140: warned and acked). ``drop``: a failure that stays
+        # one over real sockets (for_sockets)
         rows = {m["id"]: m for m in media}
-        for mid, over in (("m1", {"creator": 1, "creatorId": "card1"}), ("m2", {"name": "Cowboy Bebop"})):
+        for mid, over in (("m1", {"creator": 1, "creatorId": "card1"}), ("m2", {"name": "Cowboy Bebop", "creator": 0}),
+                          ("m3", {"creator": 1, "creatorId": FORCED_MOVE_CARD}), ("m4", {}), ("m5", {}),
+                          # no card to move and no Telegram fault: its DEPLOYED events reach Emby
+                          ("m6", {"creator": 0, "name": "🎬 Trigun"})):
             if mid not in rows:
                 rows[mid] = {"id": mid, "name": "Trigun", "creator": 0, "creatorId": "", "metadataId": "1",
                              "status": 0}
                 media.append(rows[mid])
             rows[mid].update(over)
+        flow.update({"deployed": "L-dep", "converting": "L-conv"})  # m3's card moves for these at least
         faults.append({"method": "GET", "prefix": TELEGRAM_FAULT_PREFIX, "status": rng.choice([None, 400, 500, 502]),
                        "message": rng.choice(["ECONNREFUSED", "socket hang up"]),
                        "body": '{"ok":false,"description":"Bad Request: chat not found é"}'})
         faults.append({"method": "POST", "prefix": "https://api.trello.com/1/cards/card1/actions/comments",
-                       "status": None, "message": "ETIMEDOUT", "body": '"error"'})
+                       "status": None, "message": "ETIMEDOUT", "body": '"error"', "drop": True})
+        faults.append({"method": "PUT", "prefix": "https://api.trello.com/1/cards/" + FORCED_MOVE_CARD,
+                       "status": None, "message": "ECONNRESET", "body": '"error"', "drop": True})
+        faults.append({"method": "GET", "prefix": config["instance"]["emby"]["host"] + "/emby/library/refresh",
+                       "status": None, "message": "EHOSTUNREACH", "body": '"error"', "drop": True})
+        store_faults = [{"op": "updateStatus", "id": "m4", "message": UPDATE_FAULT},
+                        {"op": "getByID", "id": "m5", "message": GET_FAULT}]
         for method, prefix in rng.sample(pool, rng.randrange(0, 4)):
             f = {"method": method, "prefix": prefix, "status": rng.choice([None, 404, 500, 502, 204]),
                  "message": rng.choice(["ECONNREFUSED", "socket hang up"]),
@@ -246,6 +280,8 @@ def make_scenario(seed: int, n_events: int = 520, mode: str = "base") -> dict:
         concurrent = {"cap": CONCURRENT_CAP, "script": [rng.randrange(2 ** 31) for _ in range(4096)]}
     msg_ids = (["m1", "m2", "m3", "m1", "m2", "missing"] if mode == "concurrent"
                else ids + ["missing", "m1", "m1", "m2"])
+    if mode == "faults":  # the rows of the forced failures, often enough for each on every seed
+        msg_ids = msg_ids + ["m2", "m3", "m4", "m5", "m6"] * 2
     events = []
     for _ in range(n_events):
         r = rng.random()
@@ -259,9 +295,12 @@ def make_scenario(seed: int, n_events: int = 520, mode: str = "base") -> dict:
             prog = rng.choice([0, 5, 45, 100, -5, 150, 2 ** 31 - 1, -2 ** 31])
             host = rng.choice(["", "", "worker-1", "ünï", "a b&c", "%s %d"])
             events.append(["progress", _P.encode((mid, st, prog, host)).hex()])
-    return {"seed": seed, "mode": mode, "config": config, "media": media, "events": events, "faults": faults,
-            "positionalArgs": "drop" if mode == "drop" else "append", "notFound": NOT_FOUND, "logLevel": "info",
-            "noTrello": mode == "no_trello", "races": races, "concurrent": concurrent}
+    sc = {"seed": seed, "mode": mode, "config": config, "media": media, "events": events, "faults": faults,
+          "positionalArgs": "drop" if mode == "drop" else "append", "notFound": NOT_FOUND, "logLevel": "info",
+          "noTrello": mode == "no_trello", "races": races, "concurrent": concurrent}
+    if store_faults:  # absent elsewhere: the other modes' scenarios serialise (and hash) as before
+        sc["storeFaults"] = store_faults
+    return sc
 
 
 def bench_scenario(n_events: int, seed: int = 0) -> dict:
@@ -347,6 +386,43 @@ class RacingStore(MemoryStore):
             self._rows[media_id] = row._replace(status=self.races[media_id])
 
 
+class StoreFault(Exception):
+    """A store call the scenario's ``storeFaults`` fails: its text is the fault's ``message``."""
+
+
+class FaultyStore(MemoryStore):
+    """The ``faults`` scenarios' media table: ``storeFaults`` entries ``{op, id, message}`` fail
+    ``updateStatus`` / ``getByID`` of that row with that text before the call touches the table,
+    so a failed update leaves the row as it was (the Node stand-in, stubs/triton-core/db.js, does
+    the same)."""
+
+    def __init__(self, medias, store_faults: List[dict]):
+        super().__init__(medias)
+        self.store_faults = {(f["op"], f["id"]): f["message"] for f in store_faults}
+
+    def update_status_nowait(self, media_id: str, status: int) -> None:
+        message = self.store_faults.get(("updateStatus", media_id))
+        if message is not None:
+            raise StoreFault(message)
+        super().update_status_nowait(media_id, status)
+
+    def get_by_id_nowait(self, media_id: str):
+        message = self.store_faults.get(("getByID", media_id))
+        if message is not None:
+            raise StoreFault(message)
+        return super().get_by_id_nowait(media_id)
+
+
+def _store_base(sc: dict):
+    """The in-process store class a scenario needs, and its constructor's second argument."""
+    assert not (sc.get("races") and sc.get("storeFaults")), "no mode has both"
+    if sc.get("races"):
+        return RacingStore, (sc["races"],)
+    if sc.get("storeFaults"):
+        return FaultyStore, (sc["storeFaults"],)
+    return MemoryStore, ()
+
+
 class _Gates:
     """Mode ``concurrent``: the gate each in-flight event's store call / sink request waits on,
     opened by :func:`_run_concurrent` in the scenario's scripted order (oracle.js ``concurrent``)."""
@@ -413,12 +489,12 @@ def run_python(sc: dict, impl: str = "python", mutate=None, suspend: bool = Fals
                   body=f["body"].encode())
     rows = [Media(id=m["id"], name=m["name"], creator=m["creator"], creatorId=m["creatorId"],
                   metadataId=m["metadataId"], status=m["status"]) for m in sc["media"]]
-    base = RacingStore if sc.get("races") else MemoryStore
+    base, extra = _store_base(sc)
     if gates is not None:
         cls = _gated_store(base, gates)
     else:
         cls = helpers.suspending(base) if suspend else base
-    store = cls(rows, sc["races"]) if base is RacingStore else cls(rows)
+    store = cls(rows, *extra)
     rig = helpers.Rig(config=config, medias=rows, no_trello=bool(sc.get("noTrello")), http=http,
                       positional_args=sc["positionalArgs"], store=store)
     if mutate is not None:
@@ -477,15 +553,30 @@ _WIRE_CARD_IDS = {"ü": "card-u", "a&b=c?d#e": "card-amp", "%20 +": "card-pct"}
 def for_sockets(sc: dict) -> dict:
     """The scenario as :func:`run_service` replays it over real sockets (``sockets=True``), for
     Node and this service alike: card ids a request line cannot hold as written are replaced, and
-    the sink faults that are transport errors (their text, e.g. ``ECONNREFUSED``, is the stand-in
-    client's, not one a real socket would give) become ``503`` answers."""
+    the random pool's sink faults that are transport errors (their text, e.g. ``ECONNREFUSED``, is
+    the stand-in client's, not one a real socket would give) become ``503`` answers.
+
+    The forced failures (``drop``) stay failures: the sink server closes the connection without
+    answering, and the fault's ``message`` becomes the text ``H1Client`` gives for that
+    (``socket hang up: <METHOD> <url without its query>``, sinks/h1.py ``_exchange``; a forced
+    fault's prefix is the request's whole URL up to the query), under the reference's origin. The
+    store faults become error replies of the Postgres server, and their ``message`` the text
+    ``pgwire.PgError`` gives for one (severity, SQLSTATE, message). Node rejects with the same
+    texts, so ``threw`` and the warn lines still compare exactly."""
     import copy
+    from beholder_amd.sinks.http import redact
+    from beholder_amd.store.pgwire import PgError
     sc = copy.deepcopy(sc)
     for m in sc["media"]:
         m["creatorId"] = _WIRE_CARD_IDS.get(m["creatorId"], m["creatorId"])
     for f in sc["faults"]:
-        if f["status"] is None:
+        if f.get("drop"):
+            assert f["status"] is None and f["method"] != "*" and "?" not in f["prefix"], f
+            f["message"] = f"socket hang up: {f['method']} {redact(f['prefix'])}"
+        elif f["status"] is None:
             f["status"] = 503
+    for f in sc.get("storeFaults") or []:
+        f["message"] = str(PgError({"S": "ERROR", "C": PG_FAULT_SQLSTATE, "M": f["message"]}))
     sc["sockets"] = True
     return sc
 
@@ -493,10 +584,20 @@ def for_sockets(sc: dict) -> dict:
 class _SinkServer:
     """One sink origin (Trello, Telegram or Emby) on 127.0.0.1, HTTP/1.1 keep-alive: records each
     request as the reference's URL (its origin + the request target) and answers from the
-    scenario's faults, first match first, as RecordingHttpClient does; else ``200 {}``."""
+    scenario's faults, first match first, as RecordingHttpClient does; else ``200 {}``.
 
-    def __init__(self, origin: str, faults: List[dict], calls: list, tls: bool = False):
+    A matching ``drop`` fault is a transport failure: the request is recorded and the connection
+    closed without an answer. ``H1Client`` sends an idempotent request (the card-move PUT, the
+    Emby GET) once more on a fresh connection when the reused one died before any response byte
+    (sinks/h1.py ``_exchange``), so one logical request may arrive twice: a dropped request
+    identical to the dropped request recorded directly before it, within one event (``mark``
+    holds the length of ``calls`` when the event was published), is not recorded again. Nothing
+    else is collapsed."""
+
+    def __init__(self, origin: str, faults: List[dict], calls: list, tls: bool = False,
+                 mark: Optional[dict] = None):
         self.origin, self.faults, self.calls, self.tls = origin, faults, calls, tls
+        self.mark = mark if mark is not None else {"start": 0, "dropped": None}
         self.port = 0
         self._server = None
 
@@ -520,7 +621,7 @@ class _SinkServer:
     def _answer(self, method: str, url: str):
         for f in self.faults:
             if (f["method"] == "*" or f["method"] == method) and url.startswith(f["prefix"]):
-                return f["status"], f["body"].encode()
+                return (None if f.get("drop") else f["status"]), f["body"].encode()
         return 200, b"{}"
 
     async def _serve(self, r, w) -> None:
@@ -541,8 +642,16 @@ class _SinkServer:
                 if n:
                     await r.readexactly(n)
                 url = self.origin + target
-                self.calls.append([method, url])
                 status, body = self._answer(method, url)
+                if status is None:  # drop: no answer; the retry of the same request counts once
+                    mark, calls = self.mark, self.calls
+                    again = (len(calls) > mark["start"] and calls[-1] is mark["dropped"]
+                             and calls[-1] == [method, url])
+                    if not again:
+                        calls.append([method, url])
+                        mark["dropped"] = calls[-1]
+                    return
+                self.calls.append([method, url])
                 if status == 204:
                     body = b""
                 w.write(b"HTTP/1.1 %d X\r\nContent-Length: %d\r\n\r\n%s" % (status, len(body), body))
@@ -553,18 +662,36 @@ class _SinkServer:
             w.close()
 
 
-def _racing_pg(races: Dict[str, int]):
+def _racing_pg(races: Dict[str, int], store_faults: Optional[List[dict]] = None):
     """tests/pg_fake.py's server with the ``reread`` scenarios' other writer: after each UPDATE of
-    a row in ``races``, a second UPDATE leaves ``races[id]`` in it (as RacingStore does)."""
+    a row in ``races``, a second UPDATE leaves ``races[id]`` in it (as RacingStore does); and with
+    the ``faults`` scenarios' store faults (as FaultyStore): the UPDATE (``updateStatus``) or
+    SELECT (``getByID``) of a fault's row is answered with an ErrorResponse carrying the fault's
+    message (``for_sockets`` left ``PgError``'s whole text there: its last part is the server's),
+    and the connection goes on serving. ``store_faults`` of the returned server can be emptied."""
+    import sqlite3
+
     from pg_fake import FakePg
+    verbs = {"UPDATE": "updateStatus", "SELECT": "getByID"}
+    head = None
+    if store_faults:
+        from beholder_amd.store.pgwire import PgError
+        head = str(PgError({"S": "ERROR", "C": PG_FAULT_SQLSTATE, "M": ""}))
 
     class RacingPg(FakePg):
         def _run(self, sql, params):
+            op = verbs.get(sql.lstrip()[:6].upper())
+            for f in self.store_faults if op and params else ():
+                if f["op"] == op and str(params[-1]) == f["id"]:
+                    assert f["message"].startswith(head), f
+                    raise sqlite3.OperationalError(f["message"][len(head):])
             out = super()._run(sql, params)
             if races and sql.lstrip()[:6].upper() == "UPDATE" and params and str(params[-1]) in races:
                 super()._run(sql, (races[str(params[-1])], params[-1]))
             return out
-    return RacingPg(auth="trust")
+    pg = RacingPg(auth="trust")
+    pg.store_faults = list(store_faults or [])
+    return pg
 
 
 def run_service(sc: dict, impl: str = "native", suspend: bool = False, sockets: bool = False,
@@ -592,6 +719,7 @@ def run_service(sc: dict, impl: str = "native", suspend: bool = False, sockets: 
     native TLS connections verify them against the bench's CA."""
     import copy
     import gc
+    import re
 
     import helpers
     from beholder_amd import topics as T
@@ -621,12 +749,12 @@ def run_service(sc: dict, impl: str = "native", suspend: bool = False, sockets: 
             http = helpers.SuspendingHttpClient() if suspend else RecordingHttpClient()
         for f in sc["faults"]:
             http.fail(f["method"], f["prefix"], status=f["status"], message=f["message"], body=f["body"].encode())
-        base = RacingStore if sc.get("races") else MemoryStore
+        base, extra = _store_base(sc)
         if gates is not None:
             cls = _gated_store(base, gates)
         else:
             cls = helpers.suspending(base) if suspend else base
-        store = cls(rows, sc["races"]) if base is RacingStore else cls(rows)
+        store = cls(rows, *extra)
     stream = MemoryStream()
     unhandled = ("unhandled error in %s handler: " % T.STATUS, "unhandled error in %s handler: " % T.PROGRESS)
 
@@ -642,13 +770,17 @@ def run_service(sc: dict, impl: str = "native", suspend: bool = False, sockets: 
                 from beholder_amd.sinks import H1Client
                 from beholder_amd.store.postgres import PostgresStore
                 calls: list = []
+                mark = {"start": 0, "dropped": None}  # _SinkServer: where the current event's calls begin
                 emby = data.get("instance", {}).get("emby", {}).get("host") or "http://emby:8096"
                 ep = emby.split("/", 3)  # scheme:, '', host[:port], base path
                 origins = {"trello": "https://api.trello.com", "telegram": "https://api.telegram.org",
                            "emby": "/".join(ep[:3])}
                 for name, origin in origins.items():
-                    servers.append(await _SinkServer(origin, sc["faults"], calls, tls=tls).start())
+                    servers.append(await _SinkServer(origin, sc["faults"], calls, tls=tls, mark=mark).start())
                 local = {n: srv.local for n, srv in zip(origins, servers)}
+                # the clients' error texts name the URL they asked: ours, read back as the reference's
+                host_back[local["trello"]] = origins["trello"]
+                host_back[local["telegram"]] = origins["telegram"]
                 d2 = copy.deepcopy(data)
                 d2["service"]["endpoints"] = {"trello": local["trello"], "telegram": local["telegram"]}
                 if "emby" in d2.get("instance", {}):
@@ -656,13 +788,14 @@ def run_service(sc: dict, impl: str = "native", suspend: bool = False, sockets: 
                     # the Emby log line names the configured host: ours, read back as the scenario's
                     host_back[d2["instance"]["emby"]["host"]] = emby
                 config = Config.from_dict(d2, env=config.env)
-                pg = await _racing_pg(sc.get("races") or {}).start()
+                pg = await _racing_pg(sc.get("races") or {}, sc.get("storeFaults")).start()
                 setup = PostgresStore(pg.dsn, create_schema=True)
                 await setup.connect()
                 for m in rows:
                     await setup.upsert(m)
                 await setup.close()
                 store = PostgresStore(pg.dsn)
+                pg_connections0 = pg.connections
                 if tls:
                     from beholder_amd.bench.http_sink_server import TLS_CERT
                     http = H1Client(timeout_s=10, ssl_cafile=TLS_CERT)
@@ -693,11 +826,11 @@ def run_service(sc: dict, impl: str = "native", suspend: bool = False, sockets: 
                 threw, logs = None, []
                 for x in map(json.loads, stream.lines[n_log:]):
                     msg = x["msg"]
+                    for ours, theirs in host_back.items():
+                        msg = re.sub(re.escape(ours) + r"(?!\d)", lambda _m, t=theirs: t, msg)
                     if x["level"] == 50 and msg.startswith(unhandled):
                         threw = msg[len(unhandled[0 if msg.startswith(unhandled[0]) else 1]):]
                         continue
-                    for ours, theirs in host_back.items():
-                        msg = msg.replace(ours, theirs)
                     logs.append([x["level"], msg])
                 return threw, logs
 
@@ -789,6 +922,8 @@ def run_service(sc: dict, impl: str = "native", suspend: bool = False, sockets: 
                 body = bytes.fromhex(hexbody)
                 svc.log.flush()
                 n_http, n_log = len(http.calls), len(stream.lines)
+                if sockets:
+                    mark["start"] = n_http
                 settled0, acked0 = _settled(settler), broker_acked()
                 broker.publish(T.STATUS if topic == "status" else T.PROGRESS, body)
                 await until(lambda: _settled(settler) > settled0 and not len(svc._inflight),
@@ -810,6 +945,10 @@ def run_service(sc: dict, impl: str = "native", suspend: bool = False, sockets: 
                 path["suspended"] = stats().get("suspended")
             await svc.close()
             if sockets:  # the table as the server holds it (the service closed its own store)
+                # connections the service's store opened: an error reply must not cost it one
+                path["pg_connections"] = pg.connections - pg_connections0
+                path["pg_pool_size"] = store.pool_size
+                pg.store_faults = []  # read every row
                 check = PostgresStore(pg.dsn)
                 await check.connect()
                 media = {m.id: (await check.get_by_id(m.id)).status for m in rows}
@@ -967,7 +1106,36 @@ def coverage(ref: dict) -> dict:
         "missing_list_warns": sum(1 for m in msgs if m.startswith("unable to find list")),
         "hook_warns": sum(1 for m in msgs if m.startswith("failed to run deployed hooks")),
         "progress_warns": sum(1 for m in msgs if m.startswith("failed to update media progress")),
+        **forced_failure_coverage(ref),
     }
+
+
+def forced_failure_coverage(ref: dict) -> dict:
+    """Events of a run that hit each failure mode ``faults`` forces (zero in the other modes),
+    read from the run's own trace; the texts are matched as substrings, so the socket form of a
+    scenario (whose texts are the production clients') counts the same."""
+    def warned(e, prefix, text=""):
+        return any(lv == 40 and m.startswith(prefix) and text in m for lv, m in e["logs"])
+
+    move = "https://api.trello.com/1/cards/" + FORCED_MOVE_CARD
+    out = dict.fromkeys(("card_move_failed_unacked", "emby_failed_after_telegram", "update_failed_unacked",
+                         "get_failed_unacked", "get_failed_progress_warned"), 0)
+    for e in ref["events"]:
+        threw, unacked = e["threw"] or "", e["acks"] == 0
+        urls = [u for _, u in e["requests"]]
+        if unacked and threw and e["requests"] and e["requests"][-1][0] == "PUT" and urls[-1].startswith(move):
+            out["card_move_failed_unacked"] += 1  # index.js:83-86 rejected: nothing after it ran
+        tg = [i for i, u in enumerate(urls) if "api.telegram.org" in u]
+        if (tg and "/emby/library/refresh" in urls[-1] and len(urls) - 1 > tg[-1] and e["acks"] == 1
+                and warned(e, "failed to run deployed hooks")):
+            out["emby_failed_after_telegram"] += 1  # index.js:99 resolved, index.js:112 rejected
+        if unacked and UPDATE_FAULT in threw:
+            out["update_failed_unacked"] += 1  # index.js:68
+        if unacked and GET_FAULT in threw:
+            out["get_failed_unacked"] += 1  # index.js:76
+        if e["acks"] == 1 and warned(e, "failed to update media progress", GET_FAULT):
+            out["get_failed_progress_warned"] += 1  # index.js:140,149-151
+    return out
 
 
 def reread_coverage(sc: dict, ref: dict) -> dict:

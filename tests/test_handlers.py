@@ -192,6 +192,22 @@ def test_status_unknown_media_leaves_unacked():
     assert r.store.update_calls == 1  # the UPDATE ran before the failing read
 
 
+def test_status_update_failure_leaves_unacked():
+    """Q1 (index.js:68): a rejected updateStatus escapes before anything else runs: no re-read,
+    no card move, no hooks, un-acked. Suspended, the compiled handler meets the failure in its
+    resume state 1."""
+    class FailingUpdate(MemoryStore):
+        def update_status_nowait(self, media_id, status):
+            raise RuntimeError("deadlock detected")
+
+    cls = helpers.suspending(FailingUpdate) if helpers.SUSPEND else FailingUpdate
+    r = Rig(store=cls([trello_media("m1", "DEPLOYED")]))
+    d, exc = r.status(status_msg("m1", "DEPLOYED"))
+    assert isinstance(exc, RuntimeError) and str(exc) == "deadlock detected" and d.state == "pending"
+    assert r.store.get_calls == 0 and r.calls() == []
+    assert r.msgs() == [f"processing status update for media m1, status: {ENUM['DEPLOYED']}"]
+
+
 def test_status_unknown_enum_trello_media_throws():
     """Q6 (index.js:74,80): unknown status -> statusText undefined -> toLowerCase throws."""
     r = Rig(medias=[trello_media("m1")])

@@ -1,4 +1,5 @@
-"""Source mutations the reference-executed gate must catch.
+"""Source mutations the reference-executed gate must catch (VERDICT r4 item 6, r5 items 1 and 5,
+r6 "Mutation A").
 
 Each case copies the package to a scratch tree, changes one line of one handler implementation
 (``handlers.py`` or its compiled twin ``ops/csrc/py_handlers.cpp``, which the scratch tree then
@@ -15,6 +16,13 @@ reach the compiled handlers' resume states, where the two resume mutations live.
 see a per-media serialisation that the reference does not have (Q9). The ``--service`` runs put
 each event through the whole consumer (AMQP broker, ``AmqpSource``, the service's dispatch, acks
 counted at the broker), where a mutation of the transport's ack flushing shows.
+
+The failures the ``faults`` scenarios force on every seed (the card-move PUT, the Emby GET,
+``updateStatus`` and ``getByID`` of existing rows) are mutated in the resume states that handle
+them; each of those mutations must fail the gate at three levels, run in its one scratch tree:
+the handlers over the suspending fakes (``FAULTS_SUSPENDED``), the whole consumer over them
+(``FAULTS_SERVICE``), and the consumer with Postgres and the sinks over TCP (``SOCKETS``), where
+the failures are a Postgres error reply and a connection closed without an answer.
 """
 import os
 import shutil
@@ -36,6 +44,10 @@ REREAD = ("--modes", "reread")
 FAULTS_SUSPENDED = ("--modes", "faults", "--suspend")
 SERVICE = ("--modes", "base", "--service")  # through the whole consumer (run_service)
 SOCKETS = ("--modes", "faults", "--service", "--sockets")  # ... with Postgres and the sinks over TCP
+FAULTS_SERVICE = ("--modes", "faults", "--service", "--suspend")  # the consumer over the suspending fakes
+# the forced failures of the faults mode show at every level: a list of options is one gate run
+# each, all in the mutation's one scratch tree (one native rebuild)
+EVERY_FAULTS_LEVEL = [FAULTS_SUSPENDED, FAULTS_SERVICE, SOCKETS]
 MUTATIONS = {
     # Q3 (index.js:94): the DEPLOYED hooks keyed off the message's status, not the re-read row's
     "hooks_off_message_status_python": (
@@ -61,6 +73,39 @@ MUTATIONS = {
         "      value = request_finish(c, value);\n      if (!value) goto catch_;",
         "      value = request_finish(c, value);\n      if (!value) { PyErr_Clear(); goto commented; }",
         FAULTS_SUSPENDED),
+    # Q1 (index.js:83-86): a card-move PUT failure the status handler resumes with (state 3) goes on
+    # to the hooks and acks ("Mutation A")
+    "card_move_failure_acks_native": (
+        "beholder_amd/ops/csrc/py_handlers.cpp",
+        "    case 3:\n      value = request_finish(c, value);\n      if (!value) return fail(c);",
+        "    case 3:\n      value = request_finish(c, value);\n      if (!value) { PyErr_Clear(); goto hooks; }",
+        EVERY_FAULTS_LEVEL),
+    # ... and the same in handlers.py: the failed move is swallowed
+    "card_move_failure_acks_python": (
+        "beholder_amd/handlers.py",
+        "                await self.trello.make_request(\"put\", _PATH_CARD(media.creatorId),\n"
+        "                                               {_Q_LIST: list_pointer, _Q_POS: _MOVE_POS})",
+        "                try:\n"
+        "                    await self.trello.make_request(\"put\", _PATH_CARD(media.creatorId),\n"
+        "                                                   {_Q_LIST: list_pointer, _Q_POS: _MOVE_POS})\n"
+        "                except Exception:  # noqa: BLE001\n"
+        "                    pass",
+        EVERY_FAULTS_LEVEL),
+    # index.js:112,120-122: an Emby failure the status handler resumes with (state 6) acks without
+    # the catch's warning
+    "emby_failure_unwarned_native": (
+        "beholder_amd/ops/csrc/py_handlers.cpp",
+        "    case 6:\n      value = request_finish(c, value);\n      if (!value) goto hooks_catch;",
+        "    case 6:\n      value = request_finish(c, value);\n"
+        "      if (!value) { PyErr_Clear(); return finish_ack(c, result); }",
+        EVERY_FAULTS_LEVEL),
+    # index.js:68: an updateStatus failure the status handler resumes with (state 1) goes on to
+    # getByID, the card move and the hooks
+    "update_status_failure_swallowed_native": (
+        "beholder_amd/ops/csrc/py_handlers.cpp",
+        "    case 1:\n      if (!value) return fail(c);\n      Py_DECREF(value);\n    updated: {",
+        "    case 1:\n      if (!value) PyErr_Clear();\n      Py_XDECREF(value);\n    updated: {",
+        EVERY_FAULTS_LEVEL),
     # the consumer path, which the handler-level gate does not run: acks settled by the handlers
     # are never scheduled for a flush over AMQP (they would leave only when the channel closes)
     "acks_never_flushed": (
@@ -80,7 +125,9 @@ MUTATIONS = {
         '        "ordering": "per_media",', ("--modes", "concurrent")),
 }
 # the mutations tests/test_handlers.py must catch too (its "suspend" cases reach the resume states)
-HANDLER_SUITE_CATCHES = ("telegram_failure_runs_emby_native", "comment_failure_counted_native")
+HANDLER_SUITE_CATCHES = ("telegram_failure_runs_emby_native", "comment_failure_counted_native",
+                         "card_move_failure_acks_native", "emby_failure_unwarned_native",
+                         "update_status_failure_swallowed_native")
 
 
 def _tree(tmp_path, mutation=None):
@@ -113,8 +160,9 @@ def _gate(tree, impl: str, modes=REREAD) -> subprocess.CompletedProcess:
                           text=True, timeout=600)
 
 
-@pytest.mark.parametrize("modes", [REREAD, FAULTS_SUSPENDED, ("--modes", "concurrent"), SERVICE, SOCKETS],
-                         ids=["reread", "faults_suspend", "concurrent", "service", "sockets"])
+@pytest.mark.parametrize("modes", [REREAD, FAULTS_SUSPENDED, ("--modes", "concurrent"), SERVICE, SOCKETS,
+                                   FAULTS_SERVICE],
+                         ids=["reread", "faults_suspend", "concurrent", "service", "sockets", "faults_service"])
 def test_unmutated_copy_passes_the_gate(tmp_path, modes):
     r = _gate(_tree(tmp_path), "python,native", modes)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
@@ -124,10 +172,13 @@ def test_unmutated_copy_passes_the_gate(tmp_path, modes):
 @pytest.mark.parametrize("name", sorted(MUTATIONS))
 def test_gate_catches_the_mutation(tmp_path, name):
     impl = "native" if name.endswith("_native") else "python" if name.endswith("_python") else "python,native"
-    r = _gate(_tree(tmp_path, name), impl, MUTATIONS[name][3])
-    assert r.returncode == 1 and "DIFF" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
-    assert "OK" not in r.stdout, r.stdout[-3000:]  # caught on every seed and implementation
-    assert "Traceback" not in r.stderr, r.stderr[-3000:]
+    tree = _tree(tmp_path, name)
+    levels = MUTATIONS[name][3]
+    for modes in levels if isinstance(levels, list) else [levels]:
+        r = _gate(tree, impl, modes)
+        assert r.returncode == 1 and "DIFF" in r.stdout, f"{modes}: " + r.stdout[-3000:] + r.stderr[-3000:]
+        assert "OK" not in r.stdout, f"{modes}: " + r.stdout[-3000:]  # caught on every seed and implementation
+        assert "Traceback" not in r.stderr, f"{modes}: " + r.stderr[-3000:]
 
 
 @pytest.mark.parametrize("name", HANDLER_SUITE_CATCHES)

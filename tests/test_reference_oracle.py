@@ -3,8 +3,13 @@ both handler implementations, event by event (``tests/reference_oracle.py`` has 
 
 Compared per event: ack count, the status listener's rejection text (Q1), whether decode threw,
 every sink request (method + full URL), every log line (level + message). At the end: counter
-values and the media table's statuses. Modes: plain, ``NO_TRELLO`` (Q2), sink faults (Q4) and
-pino@5's ``positional_args: drop`` (Q11). Skipped without ``node`` or the reference checkout.
+values and the media table's statuses. Modes: plain, ``NO_TRELLO`` (Q2), sink and store faults
+(Q1, Q4, Q7: every awaited call of index.js fails on every seed,
+``test_faults_mode_forces_every_failure``), pino@5's ``positional_args: drop`` (Q11), ``reread``
+(Q3) and ``concurrent`` (Q9); at the handler level, through the whole consumer, and over real
+sockets, where the forced failures are dropped connections and Postgres error replies. Without
+``node`` or the reference checkout the reference's side comes from the recordings under
+``tests/golden/reference_oracle/``.
 """
 import pytest
 
@@ -88,6 +93,9 @@ def test_reference_parity_over_sockets(transport):
                 assert got["path"]["direct_batches"] >= EVENTS // 2, got["path"]
                 if impl == "native":
                     assert got["path"]["suspended"] > EVENTS // 4, got["path"]
+                # an error reply (the faults mode's store faults) leaves its connection in service:
+                # the store opened its pool and nothing after it
+                assert got["path"]["pg_connections"] <= got["path"]["pg_pool_size"], got["path"]
     assert not failures, "\n".join(f"{k}: " + "\n  ".join(v) for k, v in failures.items())
 
 
@@ -104,18 +112,45 @@ def test_concurrent_scenarios_interleave():
     assert all(v > 0 for v in total.values()), total
 
 
-def test_faults_mode_fails_telegram_with_emby_on():
-    """Every ``faults`` scenario fails Telegram for some DEPLOYED rows while Emby is on (Q4,
-    index.js:92-122) and fails some comment POSTs (index.js:53-57), so a handler that runs
-    Emby after a failed Telegram call, or counts a failed comment, diverges on every seed."""
-    for seed in SEEDS:
-        sc = ro.make_scenario(seed, EVENTS, "faults")
-        ref = ro.run_node(sc)
-        reqs = [(e, m, u) for e in ref["events"] for m, u in e["requests"]]
-        failed_tg = [e for e, m, u in reqs if u.startswith(ro.TELEGRAM_FAULT_PREFIX)]
-        assert failed_tg and all(not any("/emby/" in u for _, u in e["requests"]) for e in failed_tg), seed
-        assert any("/emby/" in u for _, _, u in reqs), seed
-        assert any(u.startswith("https://api.trello.com/1/cards/card1/actions/comments") for _, _, u in reqs), seed
+def test_faults_mode_forces_every_failure():
+    """Every ``faults`` scenario, at the suite's size and at the mutation gate's
+    (tests/test_oracle_mutations.py), fails each awaited call of index.js in the reference's own
+    run, so a handler that gets any of these wrong diverges on every seed:
+
+    * Telegram for some DEPLOYED rows while Emby is on, and no Emby request follows (Q4,
+      index.js:92-122); Emby is still asked after a Telegram success;
+    * a comment POST on ``card1`` (index.js:53-57: not counted, warned, acked);
+    * the card-move PUT of the pinned card (index.js:83-86): thrown, un-acked (Q1);
+    * the Emby GET after a Telegram success (index.js:112,120-122): warned, acked;
+    * ``updateStatus`` of an existing row (index.js:68): thrown, un-acked;
+    * ``getByID`` of an existing row, in the status listener (index.js:76: un-acked) and in the
+      progress listener (index.js:140,149-151: warned, acked).
+
+    Seeds 0-4 at the suite's size and seeds 0-1 at 400 events. The socket form of each scenario
+    (``for_sockets``) keeps every one of them a failure."""
+    for events, seed in [(EVENTS, s) for s in SEEDS] + [(400, s) for s in range(2)]:
+        sc = ro.make_scenario(seed, events, "faults")
+        for form in (sc, ro.for_sockets(sc)):
+            _forced_failures_occur(form, events, seed)
+
+
+def _forced_failures_occur(form, events, seed):
+    """One scenario form: the reference's own run of it holds every forced failure."""
+    ref = ro.run_node(form)
+    assert len(ref["events"]) == events
+    reqs = [(e, m, u) for e in ref["events"] for m, u in e["requests"]]
+    failed_tg = [e for e, m, u in reqs if u.startswith(ro.TELEGRAM_FAULT_PREFIX)]
+    assert failed_tg and all(not any("/emby/" in u for _, u in e["requests"]) for e in failed_tg), seed
+    assert any("/emby/" in u for _, _, u in reqs), seed
+    assert any(u.startswith("https://api.trello.com/1/cards/card1/actions/comments") for _, _, u in reqs), seed
+    cov = ro.forced_failure_coverage(ref)
+    print(f"faults seed {seed} events {events} sockets {bool(form.get('sockets'))}: {cov}")
+    assert set(cov) == {"card_move_failed_unacked", "emby_failed_after_telegram", "update_failed_unacked",
+                        "get_failed_unacked", "get_failed_progress_warned"}
+    assert all(v >= 1 for v in cov.values()), (seed, cov)
+    # a failed updateStatus left its row as it was (no other call writes a status)
+    m4 = next(m for m in form["media"] if m["id"] == "m4")
+    assert ref["media"]["m4"] == m4["status"], seed
 
 
 def test_streams_reach_every_reference_branch():
