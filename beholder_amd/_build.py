@@ -6,7 +6,8 @@ Beholder's runtime around the Python handlers (ingest reader thread, ring,
 codec, deliveries, histograms) is C++ — see ``csrc/``. The service has no
 device kernels in its event path (the reference has none), so the runtime is a
 host build with the system C++ compiler. ``build_hip`` compiles the batched-decode kernel that
-``scripts/gpu_offload_probe.py`` measures against it (``ops/gpu_decode.py``).
+``scripts/gpu_offload_probe.py`` measures against it (``ops/gpu_decode.py``) and the stream-fold
+kernels behind ``summarise --device gpu`` (``ops/gpu_fold.py``) into one library.
 ``__graft_entry__.build()`` calls both.
 
 The HIP library is optional for the service: ``main`` builds it only when ``hipcc`` is present
@@ -207,18 +208,25 @@ def hipcc() -> str:
     return shutil.which("hipcc") or ""
 
 
+def hip_source_hash(hip_dir: str = HIP_DIR) -> str:
+    """The stamp of the HIP library: the flags, every ``*.hip`` and every header next to them
+    (an edited header must not leave a stale library)."""
+    h = hashlib.sha256(" ".join(HIP_FLAGS).encode())
+    files = [p for pat in ("*.hip", "*.hpp", "*.h") for p in glob.glob(os.path.join(hip_dir, pat))]
+    for p in sorted(files):
+        with open(p, "rb") as f:
+            h.update(os.path.basename(p).encode())
+            h.update(f.read())
+    return h.hexdigest()
+
+
 def build_hip(force: bool = False, verbose: bool = False) -> str:
     """Compile ``ops/hip/*.hip`` for gfx950 into one shared library (cached by source hash)."""
     cc = hipcc()
     if not cc:
         raise RuntimeError("hipcc not found (ROCm is required to build the HIP extension)")
     srcs = sorted(glob.glob(os.path.join(HIP_DIR, "*.hip")))
-    h = hashlib.sha256(" ".join(HIP_FLAGS).encode())
-    for p in srcs:
-        with open(p, "rb") as f:
-            h.update(os.path.basename(p).encode())
-            h.update(f.read())
-    digest = h.hexdigest()
+    digest = hip_source_hash()
     stamp = HIP_TARGET + ".srchash"
     if not force and _stamp_matches(HIP_TARGET, stamp, digest):
         return HIP_TARGET

@@ -6,6 +6,7 @@ run      start the service (``--source amqp|stdin|file``); the reference's only 
 config   validate and print the effective config (secrets masked).
 gen      write synthetic framed telemetry to stdout/a file (+ optional media fixture).
 decode   turn a framed stream into NDJSON (debugging).
+summarise  fold a framed stream into its end state: counters, comments, final statuses (``replay``).
 seed     load a media fixture into a sqlite/postgres store.
 bench    run the BASELINE.json measurement configs (see ``beholder_amd.bench.harness``).
 publish  publish a framed stream to an AMQP broker.
@@ -236,6 +237,35 @@ def cmd_decode(a: argparse.Namespace) -> int:
     return 0
 
 
+def cmd_summarise(a: argparse.Namespace) -> int:
+    """What the service will have done once this stream has gone through (``beholder_amd.replay``)."""
+    import io
+
+    from . import replay
+    if a.device == "gpu":
+        try:
+            import torch
+
+            from .ops import gpu_fold
+            if not torch.cuda.is_available():
+                raise RuntimeError("no GPU is visible")
+            gpu_fold.lib()
+        except (ImportError, RuntimeError, OSError) as e:
+            print(f"beholder: --device gpu is not available ({e}); use --device cpu", file=sys.stderr)
+            return 1
+    try:
+        source = a.input if a.input else io.BytesIO(sys.stdin.buffer.read())
+        summary = replay.fold_file(source, device=a.device, dialect=a.dialect, chunk_bytes=a.chunk_bytes)
+    except ValueError as e:
+        print(f"beholder: {e}", file=sys.stderr)
+        return 1
+    out = {"summary": summary.to_json()}
+    if a.media_fixture:
+        out["prediction"] = summary.apply(_load_fixture(a.media_fixture))
+    print(json.dumps(out))
+    return 0
+
+
 def cmd_seed(a: argparse.Namespace) -> int:
     from .store import open_store
 
@@ -315,6 +345,15 @@ def build_parser() -> argparse.ArgumentParser:
     d = sub.add_parser("decode", help="framed stream -> NDJSON")
     d.add_argument("input", nargs="?")
     d.set_defaults(fn=cmd_decode)
+
+    z = sub.add_parser("summarise", help="framed stream -> what the service will have done with it (JSON)")
+    z.add_argument("input", nargs="?")
+    z.add_argument("--device", choices=["cpu", "gpu"], default="cpu",
+                   help="cpu: the definition, runs anywhere; gpu: the gfx950 fold kernels")
+    z.add_argument("--dialect", choices=["protobufjs", "upb"], default="protobufjs")
+    z.add_argument("--media-fixture", help="JSON list of media rows: also print the prediction for them")
+    z.add_argument("--chunk-bytes", type=int, default=256 << 20, help="fold the input in pieces of this size")
+    z.set_defaults(fn=cmd_summarise)
 
     s = sub.add_parser("seed", help="load a media fixture into a store")
     s.add_argument("fixture")

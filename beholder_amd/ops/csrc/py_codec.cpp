@@ -673,7 +673,62 @@ PyObject* mod_materialise_table(PyObject*, PyObject* const* a, Py_ssize_t n) {
   return out;
 }
 
+// frame_index(buf) -> (n, offs)
+// Host half of the GPU fold (ops/gpu_fold.py, beholder_amd/replay.py): one pass over the length
+// headers of a framed stream (`u32 L | u8 topic | body`, transport/framing.py). `offs` is a
+// bytearray of n + 1 int32 frame starts, offs[n] == len(buf); no body is copied or looked at.
+// Raises ValueError where framing.iter_frames does (a truncated header, L == 0, a frame past the
+// end) and for a buffer of 2^31 bytes or more, which int32 offsets cannot index.
+// frame_index(buf, True) indexes the whole frames at the front of a buffer that may end inside one
+// (a file read in pieces, replay.iter_chunks): it stops there instead of raising, and offs[n] is
+// the number of bytes those frames take. L == 0 is an error in both forms.
+PyObject* mod_frame_index(PyObject*, PyObject* args) {
+  PyObject* arg;
+  int partial = 0;
+  if (!PyArg_ParseTuple(args, "O|p:frame_index", &arg, &partial)) return nullptr;
+  Py_buffer b;
+  if (PyObject_GetBuffer(arg, &b, PyBUF_SIMPLE) < 0) return nullptr;
+  PyObject* out = nullptr;
+  const uint8_t* p = static_cast<const uint8_t*>(b.buf);
+  const uint64_t len = uint64_t(b.len);
+  if (len >= (uint64_t(1) << 31)) {
+    PyErr_SetString(PyExc_ValueError, "buffer of 2^31 bytes or more: fold it in chunks");
+  } else {
+    std::vector<int32_t> offs;
+    offs.reserve(size_t(len / 48) + 2);
+    uint64_t i = 0;
+    const char* err = nullptr;
+    while (i < len) {
+      if (len - i < 4) {
+        if (!partial) err = "truncated frame header";
+        break;
+      }
+      const uint32_t L = uint32_t(p[i]) | uint32_t(p[i + 1]) << 8 | uint32_t(p[i + 2]) << 16 | uint32_t(p[i + 3]) << 24;
+      if (L == 0 || len - i - 4 < L) {
+        if (L == 0 || !partial) err = "truncated or empty frame";
+        break;
+      }
+      offs.push_back(int32_t(i));
+      i += 4 + uint64_t(L);
+    }
+    if (err) {
+      PyErr_SetString(PyExc_ValueError, err);
+    } else {
+      offs.push_back(int32_t(i));  // == len unless partial
+      PyObject* arr = PyByteArray_FromStringAndSize(reinterpret_cast<const char*>(offs.data()),
+                                                    Py_ssize_t(offs.size() * sizeof(int32_t)));
+      if (arr) {
+        out = Py_BuildValue("(nN)", Py_ssize_t(offs.size() - 1), arr);
+      }
+    }
+  }
+  PyBuffer_Release(&b);
+  return out;
+}
+
 PyMethodDef codec_functions[] = {
+    {"frame_index", mod_frame_index, METH_VARARGS,
+     "frame_index(buf, partial=False) -> (n, bytearray of n + 1 int32 frame starts)"},
     {"materialise_table", reinterpret_cast<PyCFunction>(reinterpret_cast<void (*)(void)>(mod_materialise_table)),
      METH_FASTCALL, "materialise_table(buf, table) -> list of (mediaId, status, progress, host) or None"},
     {nullptr, nullptr, 0, nullptr}};
