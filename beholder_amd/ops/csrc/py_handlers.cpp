@@ -639,15 +639,17 @@ PyObject* request_finish(CallObject* c, PyObject* value) {
   // raise_for_status() call (it only raises for a non-2xx status)
   PyObject* rt = reinterpret_cast<PyObject*>(h1_response_type());
   long code = -1;
+  PyObject* slot_st = nullptr;  // borrowed from the stock response's slot
   if (rt && reinterpret_cast<PyObject*>(Py_TYPE(value)) == rt) {
-    PyObject* st = h1_response_status(value);
-    if (st && PyLong_CheckExact(st)) {
-      code = PyLong_AsLong(st);
+    slot_st = h1_response_status(value);
+    if (slot_st && PyLong_CheckExact(slot_st)) {
+      code = PyLong_AsLong(slot_st);
       if (code == -1 && PyErr_Occurred()) PyErr_Clear();
     }
   }
   if (stats) {
-    PyObject* st = PyObject_GetAttr(value, s_status);
+    // the slot's object is what `value.status` reads for the stock type
+    PyObject* st = slot_st ? Py_NewRef(slot_st) : PyObject_GetAttr(value, s_status);
     bool ok = st && record_stats(stats, st, dt);
     Py_XDECREF(st);
     Py_DECREF(stats);

@@ -13,6 +13,9 @@
 //   p.feed(data) -> None | (status, reason, raw_headers, body, keep_alive)
 //   p.eof()      -> None | (...)  # peer closed: completes a close-delimited body
 //
+// A reply that arrives whole in one feed() while nothing is buffered is parsed in the caller's
+// memory (parse_inplace, counted by `inplace`); every other input goes through the buffer.
+//
 // Malformed input raises ValueError; the connection must then be discarded.
 // Bytes after a complete response stay buffered (`buffered`), which a
 // non-pipelining client treats as a protocol error.
@@ -45,14 +48,25 @@ struct H1ParserObject {
   PyObject* last_reason;   // the last reply's reason / raw headers / body objects (reuse_or_make)
   PyObject* last_headers;
   PyObject* last_body;
+  uint64_t inplace;  // replies parsed straight out of the fed chunk (parse_inplace)
 };
 
 PyTypeObject H1ParserType = {PyVarObject_HEAD_INIT(nullptr, 0)};
 
-inline bool is_tchar(unsigned char c) {
-  return (c >= 'a' && c <= 'z') || (c >= 'A' && c <= 'Z') || (c >= '0' && c <= '9') ||
-         std::strchr("!#$%&'*+-.^_`|~", c) != nullptr;
-}
+// RFC 9110 token characters, as a table: header names are checked byte by byte on every reply.
+struct TcharTable {
+  bool v[256];
+  constexpr TcharTable() : v() {
+    for (int c = 'a'; c <= 'z'; ++c) v[c] = true;
+    for (int c = 'A'; c <= 'Z'; ++c) v[c] = true;
+    for (int c = '0'; c <= '9'; ++c) v[c] = true;
+    const char extra[] = "!#$%&'*+-.^_`|~";
+    for (int i = 0; extra[i]; ++i) v[static_cast<unsigned char>(extra[i])] = true;
+  }
+};
+constexpr TcharTable kTchar;
+
+inline bool is_tchar(unsigned char c) { return kTchar.v[c]; }
 
 inline unsigned char lower(unsigned char c) { return (c >= 'A' && c <= 'Z') ? c + 32 : c; }
 
@@ -334,7 +348,7 @@ bool run(H1ParserObject* s) {
 // An immutable object equal to the last one made from the same field, or a new one (then kept).
 // A keep-alive connection's replies mostly repeat the reason phrase and often the headers and
 // body, so most replies reuse the objects (they are immutable: sharing is invisible).
-PyObject* reuse_or_make(PyObject** cache, const std::string& v, bool text) {
+PyObject* reuse_or_make(PyObject** cache, const char* v, size_t vn, bool text) {
   PyObject* c = *cache;
   if (c) {
     const char* d;
@@ -346,30 +360,30 @@ PyObject* reuse_or_make(PyObject** cache, const std::string& v, bool text) {
       d = PyBytes_AS_STRING(c);
       n = PyBytes_GET_SIZE(c);
     }
-    if (size_t(n) == v.size() && memcmp(d, v.data(), v.size()) == 0) return Py_NewRef(c);
+    if (size_t(n) == vn && memcmp(d, v, vn) == 0) return Py_NewRef(c);
   }
   PyObject* o;
   if (text) {
     // reason phrases are opaque octets: UTF-8 when they are, else latin-1
-    o = PyUnicode_DecodeUTF8(v.data(), Py_ssize_t(v.size()), nullptr);
+    o = PyUnicode_DecodeUTF8(v, Py_ssize_t(vn), nullptr);
     if (!o) {
       PyErr_Clear();
-      o = PyUnicode_DecodeLatin1(v.data(), Py_ssize_t(v.size()), nullptr);
+      o = PyUnicode_DecodeLatin1(v, Py_ssize_t(vn), nullptr);
     }
     if (o && !PyUnicode_IS_ASCII(o)) return o;  // only ASCII ones are cached (compared bytewise above)
   } else {
-    o = PyBytes_FromStringAndSize(v.data(), Py_ssize_t(v.size()));
+    o = PyBytes_FromStringAndSize(v, Py_ssize_t(vn));
   }
   if (!o) return nullptr;
-  if (v.size() <= 4096) Py_XSETREF(*cache, Py_NewRef(o));
+  if (vn <= 4096) Py_XSETREF(*cache, Py_NewRef(o));
   return o;
 }
 
-PyObject* make_result(H1ParserObject* s) {
-  PyObject* st = PyLong_FromLong(s->status);
-  PyObject* reason = st ? reuse_or_make(&s->last_reason, *s->reason, true) : nullptr;
-  PyObject* hdr = reason ? reuse_or_make(&s->last_headers, *s->headers, false) : nullptr;
-  PyObject* body = hdr ? reuse_or_make(&s->last_body, *s->body, false) : nullptr;
+PyObject* reuse_or_make(PyObject** cache, const std::string& v, bool text) {
+  return reuse_or_make(cache, v.data(), v.size(), text);
+}
+
+PyObject* result_tuple(PyObject* st, PyObject* reason, PyObject* hdr, PyObject* body, bool keep_alive) {
   PyObject* r = body ? PyTuple_New(5) : nullptr;
   if (!r) {
     Py_XDECREF(st);
@@ -382,7 +396,17 @@ PyObject* make_result(H1ParserObject* s) {
   PyTuple_SET_ITEM(r, 1, reason);
   PyTuple_SET_ITEM(r, 2, hdr);
   PyTuple_SET_ITEM(r, 3, body);
-  PyTuple_SET_ITEM(r, 4, Py_NewRef(s->keep_alive ? Py_True : Py_False));
+  PyTuple_SET_ITEM(r, 4, Py_NewRef(keep_alive ? Py_True : Py_False));
+  return r;
+}
+
+PyObject* make_result(H1ParserObject* s) {
+  PyObject* st = PyLong_FromLong(s->status);
+  PyObject* reason = st ? reuse_or_make(&s->last_reason, *s->reason, true) : nullptr;
+  PyObject* hdr = reason ? reuse_or_make(&s->last_headers, *s->headers, false) : nullptr;
+  PyObject* body = hdr ? reuse_or_make(&s->last_body, *s->body, false) : nullptr;
+  PyObject* r = result_tuple(st, reason, hdr, body, s->keep_alive);
+  if (!r) return nullptr;
   ++s->responses;
   s->st = St::IDLE;
   s->body->clear();
@@ -390,6 +414,86 @@ PyObject* make_result(H1ParserObject* s) {
     s->buf->clear();
     s->pos = 0;
   }
+  return r;
+}
+
+// The whole reply in one chunk, nothing buffered: parsed where it lies, in one forward pass,
+// without buf / headers / body. Only replies for which run() + make_result() provably give the
+// same tuple are taken: CRLF line ends throughout, a final status, plain header lines, at most
+// one well-formed Content-Length, no Transfer-Encoding, and exactly head + body bytes. Anything
+// else sets *fallback before any state changes, and the buffered path decides (and words the
+// errors). Keeps no pointer into `data`.
+PyObject* parse_inplace(H1ParserObject* s, const char* data, size_t n, bool* fallback) {
+  *fallback = true;
+  const char* const lim = data + n;
+  const char* e = static_cast<const char*>(std::memchr(data, '\n', n));
+  if (!e || e - data < 13 || e[-1] != '\r') return nullptr;
+  const char* p = data;
+  size_t ln = size_t(e - data) - 1;
+  if (std::memcmp(p, "HTTP/1.", 7) != 0 || p[7] < '0' || p[7] > '9' || p[8] != ' ') return nullptr;
+  for (int i = 9; i < 12; ++i)
+    if (p[i] < '0' || p[i] > '9') return nullptr;
+  int status = (p[9] - '0') * 100 + (p[10] - '0') * 10 + (p[11] - '0');
+  if (status < 200) return nullptr;  // interim replies, 101, malformed codes
+  if (ln > 12 && p[12] != ' ') return nullptr;
+  const bool http11 = p[7] >= '1';
+  const char* reason = ln > 13 ? p + 13 : p + ln;
+  size_t reason_n = ln > 13 ? ln - 13 : 0;
+
+  const char* const hdr = e + 1;
+  const char* line = hdr;
+  bool conn_close = false, conn_keep = false, has_cl = false;
+  uint64_t cl = 0;
+  for (;;) {
+    e = static_cast<const char*>(std::memchr(line, '\n', size_t(lim - line)));
+    if (!e || e == line || e[-1] != '\r') return nullptr;
+    ln = size_t(e - line) - 1;
+    if (ln == 0) break;  // the blank line
+    if (*line == ' ' || *line == '\t') return nullptr;
+    size_t nn = 0;
+    while (nn < ln && is_tchar(static_cast<unsigned char>(line[nn]))) ++nn;
+    if (nn == 0 || nn == ln || line[nn] != ':') return nullptr;
+    const char* v = line + nn + 1;
+    size_t vn = ln - nn - 1;
+    if (nn == 14) {
+      if (ieq(line, nn, "content-length")) {
+        trim(v, vn);
+        if (has_cl || vn == 0 || vn > 18) return nullptr;
+        for (size_t i = 0; i < vn; ++i) {
+          if (v[i] < '0' || v[i] > '9') return nullptr;
+          cl = cl * 10 + uint64_t(v[i] - '0');
+        }
+        has_cl = true;
+      }
+    } else if (nn == 17) {
+      if (ieq(line, nn, "transfer-encoding")) return nullptr;
+    } else if (nn == 10) {
+      if (ieq(line, nn, "connection")) {
+        trim(v, vn);
+        if (has_token(v, vn, "close")) conn_close = true;
+        if (has_token(v, vn, "keep-alive")) conn_keep = true;
+      }
+    }
+    line = e + 1;
+  }
+  const char* const body = e + 1;
+  if (size_t(body - data) > s->max_header) return nullptr;  // near the limit: the old checks decide
+  size_t body_n = size_t(lim - body);
+  if (s->head_req || status == 204 || status == 304) {
+    if (body_n) return nullptr;
+  } else {
+    if (!has_cl || cl > s->max_body || cl != body_n) return nullptr;
+  }
+  *fallback = false;
+  PyObject* st = PyLong_FromLong(status);
+  PyObject* ro = st ? reuse_or_make(&s->last_reason, reason, reason_n, true) : nullptr;
+  PyObject* ho = ro ? reuse_or_make(&s->last_headers, hdr, size_t(line - hdr), false) : nullptr;
+  PyObject* bo = ho ? reuse_or_make(&s->last_body, body, body_n, false) : nullptr;
+  PyObject* r = result_tuple(st, ro, ho, bo, http11 ? !conn_close : (conn_keep && !conn_close));
+  if (!r) return nullptr;
+  ++s->responses;
+  ++s->inplace;
+  s->st = St::IDLE;
   return r;
 }
 
@@ -420,6 +524,7 @@ PyObject* h1_new(PyTypeObject* type, PyObject*, PyObject*) {
   s->st = St::IDLE;
   s->head_req = false;
   s->responses = 0;
+  s->inplace = 0;
   reset_response(s);
   return reinterpret_cast<PyObject*>(s);
 }
@@ -484,6 +589,11 @@ PyObject* h1_start(H1ParserObject* s, PyObject* const* args, Py_ssize_t nargs, P
 
 PyObject* feed_core(H1ParserObject* s, const char* data, size_t n) {
   BEHOLDER_TRY {
+    if (s->st == St::HEAD && s->buf->empty()) {
+      bool fallback;
+      PyObject* r = parse_inplace(s, data, n, &fallback);
+      if (!fallback) return r;
+    }
     s->buf->append(data, n);
     bool done;
     try {
@@ -531,6 +641,7 @@ PyObject* h1_eof(H1ParserObject* s, PyObject*) {
 
 PyObject* h1_get_buffered(H1ParserObject* s, void*) { return PyLong_FromSize_t(s->buf->size() - s->pos); }
 PyObject* h1_get_responses(H1ParserObject* s, void*) { return PyLong_FromUnsignedLongLong(s->responses); }
+PyObject* h1_get_inplace(H1ParserObject* s, void*) { return PyLong_FromUnsignedLongLong(s->inplace); }
 PyObject* h1_get_idle(H1ParserObject* s, void*) { return PyBool_FromLong(s->st == St::IDLE); }
 PyObject* h1_get_started(H1ParserObject* s, void*) {
   // any byte of the current response received yet (a reused connection that fails
@@ -550,6 +661,7 @@ PyMethodDef h1_methods[] = {
 PyGetSetDef h1_getset[] = {
     {"buffered", reinterpret_cast<getter>(h1_get_buffered), nullptr, "unconsumed input bytes", nullptr},
     {"responses", reinterpret_cast<getter>(h1_get_responses), nullptr, "complete responses parsed", nullptr},
+    {"inplace", reinterpret_cast<getter>(h1_get_inplace), nullptr, "responses parsed in place, without buffering", nullptr},
     {"idle", reinterpret_cast<getter>(h1_get_idle), nullptr, "no response expected", nullptr},
     {"started", reinterpret_cast<getter>(h1_get_started), nullptr, "bytes of the current response seen", nullptr},
     {nullptr, nullptr, nullptr, nullptr, nullptr}};
