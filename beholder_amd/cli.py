@@ -246,10 +246,10 @@ def cmd_summarise(a: argparse.Namespace) -> int:
         try:
             import torch
 
-            from .ops import gpu_fold
+            from .ops import gpu_fold, hip_lib  # noqa: F401  gpu_fold: its imports fail here, not mid-run
             if not torch.cuda.is_available():
                 raise RuntimeError("no GPU is visible")
-            gpu_fold.lib()
+            hip_lib.lib()
         except (ImportError, RuntimeError, OSError) as e:
             print(f"beholder: --device gpu is not available ({e}); use --device cpu", file=sys.stderr)
             return 1

@@ -16,37 +16,18 @@ on malformed input the kernel agrees with production: ``ok == 0`` exactly where
 :func:`reference_decode_pbjs` are plain-Python definitions of the table; the GPU tests compare
 the kernel against them and against the service's own protobufjs codec.
 
-The extension is built in-tree by ``beholder_amd._build.build_hip`` (hipcc, gfx950) and loaded
-with ctypes after ``import torch``. torch's HIP runtime has the same soname, so the kernel
-launches on torch's runtime and stream. A missing library raises; there is no CPU fallback
+The extension is loaded by ``ops/hip_lib.py``. A missing library raises; there is no CPU fallback
 behind :func:`decode_batch`.
 """
 from __future__ import annotations
 
-import ctypes
-import os
 from typing import List, Sequence, Tuple
 
 import numpy as np
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hip", "libbeholder_hip.so")
-FIELDS = ("id_off", "id_len", "status", "progress", "host_off", "host_len", "ok", "seen")
-DIALECT_IDS = {"upb": 0, "protobufjs": 1}  # the kernel's DIALECT_* constants
-_lib = None
+from . import hip_lib
 
-
-def lib() -> ctypes.CDLL:
-    """The HIP extension (raises if it was not built: no silent fallback)."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(f"{LIB_PATH} is missing: build it with `python -m beholder_amd.ops.build`")
-        import torch  # noqa: F401  load torch's libamdhip64 first so the kernel shares its runtime
-        _lib = ctypes.CDLL(LIB_PATH)
-        _lib.bh_decode_telemetry.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-                                             ctypes.c_void_p, ctypes.c_int]
-        _lib.bh_decode_telemetry.restype = ctypes.c_int
-    return _lib
+FIELDS = ("id_off", "id_len", "status", "progress", "host_off", "host_len", "ok", "seen")  # the kernel's Row
 
 
 def pack(bodies: Sequence[bytes]) -> Tuple[bytes, np.ndarray]:
@@ -71,12 +52,8 @@ def decode_batch(buf_dev, offs_dev, n: int, out_dev=None, dialect: str = "protob
     ``n + 1`` host-checked boundaries) on the current torch stream, in ``dialect``. Returns the
     ``(n, 8)`` int32 table (``out_dev`` if given)."""
     import torch
-    if dialect not in DIALECT_IDS:
-        raise ValueError(f"unknown dialect {dialect!r} ({'|'.join(DIALECT_IDS)})")
-    if buf_dev.dtype != torch.uint8 or offs_dev.dtype != torch.int32 or offs_dev.numel() != n + 1:
-        raise ValueError("decode_batch needs uint8 buf, int32 offs of n + 1")
-    if not (buf_dev.is_cuda and offs_dev.is_cuda and buf_dev.is_contiguous() and offs_dev.is_contiguous()):
-        raise ValueError("decode_batch needs contiguous device tensors")
+    dialect_id = hip_lib.check_dialect(dialect)
+    hip_lib.check_device_tensors(buf_dev, offs_dev, n)
     if out_dev is None:
         out_dev = torch.empty((n, 8), dtype=torch.int32, device=buf_dev.device)
     elif out_dev.shape != (n, 8) or out_dev.dtype != torch.int32 or not out_dev.is_contiguous():
@@ -84,8 +61,8 @@ def decode_batch(buf_dev, offs_dev, n: int, out_dev=None, dialect: str = "protob
     if n == 0:
         return out_dev
     stream = torch.cuda.current_stream(buf_dev.device).cuda_stream
-    err = lib().bh_decode_telemetry(buf_dev.data_ptr(), offs_dev.data_ptr(), n, out_dev.data_ptr(), stream,
-                                    DIALECT_IDS[dialect])
+    err = hip_lib.lib().bh_decode_telemetry(buf_dev.data_ptr(), offs_dev.data_ptr(), n, out_dev.data_ptr(), stream,
+                                            dialect_id)
     if err:
         raise RuntimeError(f"bh_decode_telemetry launch failed: hipError {err}")
     return out_dev

@@ -16,37 +16,20 @@ The stages, which ``scripts/gpu_fold_probe.py`` times one by one:
    the *decoded* string; in the upb dialect also non-ASCII hosts and groups) with the service's
    codec.
 
-The extension is built in-tree by ``beholder_amd._build.build_hip`` (hipcc, gfx950) and loaded with
-ctypes after ``import torch``, as ``ops/gpu_decode.py`` does. A missing library raises; there is no
-CPU fallback behind :func:`fold`.
+The extension is loaded by ``ops/hip_lib.py``. A missing library raises; there is no CPU fallback
+behind :func:`fold`.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Dict, NamedTuple, Optional, Tuple
 
 import numpy as np
 
-from . import gpu_decode
+from . import hip_lib
 
-DIALECT_IDS = gpu_decode.DIALECT_IDS
 ALL_ONES = 0xFFFFFFFFFFFFFFFF
 # counters[] of telemetry_fold.hip
 C_STATUS_ERR, C_PROGRESS_ERR, C_UNKNOWN_STATUS, C_OTHER_TOPIC, C_OVERFLOW, C_HIST, N_COUNTERS = 0, 1, 2, 3, 4, 8, 72
-_ready = False
-
-
-def lib() -> ctypes.CDLL:
-    """The HIP extension with the fold's entry point declared (raises if it was not built)."""
-    global _ready
-    so = gpu_decode.lib()
-    if not _ready:
-        so.bh_fold_telemetry.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                         ctypes.c_ulonglong, ctypes.c_ulonglong] + [ctypes.c_void_p] * 6 + \
-                                        [ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p]
-        so.bh_fold_telemetry.restype = ctypes.c_int
-        _ready = True
-    return so
 
 
 def hash64(b: bytes) -> int:
@@ -112,11 +95,9 @@ def upload(data, offs: np.ndarray, device="cuda") -> Tuple[object, object]:
 def allocate(buf_dev, offs_dev, n: int) -> Tables:
     """Zeroed tables for ``n`` frames next to ``buf_dev``. Checks the arguments on the host."""
     import torch
-    if buf_dev.dtype != torch.uint8 or offs_dev.dtype != torch.int32 or offs_dev.numel() != n + 1 or n < 1:
-        raise ValueError("the fold needs a uint8 buf and int32 offs of n + 1, n >= 1")
-    if not (buf_dev.is_cuda and offs_dev.is_cuda and buf_dev.is_contiguous() and offs_dev.is_contiguous()
-            and buf_dev.device == offs_dev.device):
-        raise ValueError("the fold needs contiguous tensors on one device")
+    hip_lib.check_device_tensors(buf_dev, offs_dev, n)
+    if n < 1:
+        raise ValueError("the fold needs n >= 1")
     if buf_dev.numel() >= 2 ** 31:
         raise ValueError("stream too large for int32 offsets")
     dev = buf_dev.device
@@ -134,14 +115,13 @@ def launch(t: Tables, dialect: str = "protobufjs", mask: int = 0, hash_mask: int
     """Pass A and/or pass B (``passes`` 1, 2 or 3) over ``t`` on the current torch stream. ``t.offs``
     must come from :func:`index`: the kernels trust it."""
     import torch
-    if dialect not in DIALECT_IDS:
-        raise ValueError(f"unknown dialect {dialect!r} ({'|'.join(DIALECT_IDS)})")
+    dialect_id = hip_lib.check_dialect(dialect)
     if not 0 <= hash_mask <= ALL_ONES or not 0 <= mask <= ALL_ONES or passes not in (1, 2, 3):
         raise ValueError("hash_mask and the status mask are 64-bit, passes is 1, 2 or 3")
-    so = lib()
+    so = hip_lib.lib()
     with torch.cuda.device(t.buf.device):
         stream = torch.cuda.current_stream().cuda_stream
-        err = so.bh_fold_telemetry(t.buf.data_ptr(), t.offs.data_ptr(), t.n, DIALECT_IDS[dialect], mask, hash_mask,
+        err = so.bh_fold_telemetry(t.buf.data_ptr(), t.offs.data_ptr(), t.n, dialect_id, mask, hash_mask,
                                    t.rows.data_ptr(), t.counters.data_ptr(), t.overflow.data_ptr(),
                                    t.claim.data_ptr(), t.last.data_ptr(), t.counts.data_ptr(), t.slots, passes, stream)
     if err:
@@ -204,14 +184,13 @@ def fold(data, device="cuda", dialect: str = "protobufjs", hash_mask: Optional[i
     """``(Summary, frames folded on the host)`` of a framed stream through the device."""
     from .. import replay
     import torch
-    if dialect not in DIALECT_IDS:
-        raise ValueError(f"unknown dialect {dialect!r} ({'|'.join(DIALECT_IDS)})")
+    hip_lib.check_dialect(dialect)
     if torch.device(device).type != "cuda":
         raise ValueError(f"fold needs a GPU device, not {device!r}")
     n, offs = index(data)
     if n == 0:
         return replay.Summary(), 0
-    lib()  # a missing library raises before anything is uploaded
+    hip_lib.lib()  # a missing library raises before anything is uploaded
     buf, offs_dev = upload(data, offs, device)
     t = allocate(buf, offs_dev, n)
     launch(t, dialect, known_mask(replay.status_names()), ALL_ONES if hash_mask is None else hash_mask)

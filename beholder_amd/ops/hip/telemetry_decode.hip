@@ -10,9 +10,9 @@
 // Layout: `buf` holds the concatenated message bodies, `offs[n + 1]` their boundaries (checked
 // on the host: offs[0] = 0, non-decreasing, offs[n] = bytes in buf). One lane per message: the
 // work is a varint state machine with data-dependent branches, so a 64-wide wavefront decodes 64
-// messages side by side and diverges where their layouts differ. Each lane emits 8 int32:
-//   [id_off, id_len, status, progress, host_off, host_len, ok, fields_seen]
-// (offsets are absolute in buf; ok = 0 where the CPU codec raises DecodeError).
+// messages side by side and diverges where their layouts differ. Each lane emits one Row, 8 int32:
+//   {id_off, id_len, status, progress, host_off, host_len, ok, seen}
+// (offsets are absolute in buf; ok = OK_ERROR, 0, where the CPU codec raises DecodeError).
 //
 // The readers, their two dialects (protobufjs, the service's default, and upb) and the message
 // types they know are in telemetry_readers.hpp, shared with telemetry_fold.hip. This kernel reads
@@ -31,13 +31,10 @@ __global__ __launch_bounds__(256) void decode_telemetry(const uint8_t* __restric
   if (m >= n) return;
   const int start = offs[m];
   const int end = offs[m + 1];
-  int r[8] = {0, 0, 0, 0, 0, 0, 1, 0};
-  if (DIALECT == DIALECT_PROTOBUFJS)
-    decode_pbjs<MSG_PROGRESS>(buf, start, end, r);
-  else
-    decode_upb<MSG_PROGRESS, false>(buf, start, end, r);
-  out[2 * m] = make_int4(r[0], r[1], r[2], r[3]);
-  out[2 * m + 1] = make_int4(r[4], r[5], r[6], r[7]);
+  Row r;
+  read_message<DIALECT, false>(buf, start, end, false, r);  // a TelemetryProgress, upb in its plain form
+  out[2 * m] = make_int4(r.id_off, r.id_len, r.status, r.progress);
+  out[2 * m + 1] = make_int4(r.host_off, r.host_len, r.ok, r.seen);
 }
 
 }  // namespace

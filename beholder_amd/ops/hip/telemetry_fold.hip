@@ -53,6 +53,7 @@ constexpr uint32_t F_KNOWN = 4;   // progress: status is a known enum number
 // counters[]: ops/gpu_fold.py reads the same layout
 constexpr int C_STATUS_ERR = 0, C_PROGRESS_ERR = 1, C_UNKNOWN_STATUS = 2, C_OTHER_TOPIC = 3, C_OVERFLOW = 4;
 constexpr int C_HIST = 8, N_COUNTERS = C_HIST + 64;
+static_assert(N_COUNTERS == 72, "ops/gpu_fold.py allocates N_COUNTERS = 72 counters");
 
 constexpr int TOPIC_STATUS = 1, TOPIC_PROGRESS = 2;
 
@@ -98,32 +99,27 @@ __global__ __launch_bounds__(256) void fold_decode(const uint8_t* __restrict__ b
       atomicAdd(&local[C_OTHER_TOPIC], 1u);
     } else {
       const bool is_status = topic == TOPIC_STATUS;
-      int r[8] = {0, 0, 0, 0, 0, 0, 1, 0};
-      if (DIALECT == DIALECT_PROTOBUFJS) {
-        if (is_status) decode_pbjs<MSG_STATUS>(buf, start, end, r);
-        else decode_pbjs<MSG_PROGRESS>(buf, start, end, r);
-      } else {
-        if (is_status) decode_upb<MSG_STATUS, true>(buf, start, end, r);
-        else decode_upb<MSG_PROGRESS, true>(buf, start, end, r);
-      }
-      bool to_host = r[6] == OK_HOST;
-      if (r[6] == 1) {
+      Row r;
+      read_message<DIALECT, true>(buf, start, end, is_status, r);
+      bool to_host = r.ok == OK_HOST;
+      if (r.ok == OK_DECODED) {
         uint32_t high;
-        row.hash = hash_bytes(buf + r[0], r[1], high);
+        row.hash = hash_bytes(buf + r.id_off, r.id_len, high);
         to_host = high != 0;
-        if (DIALECT == DIALECT_UPB && !is_status && !to_host) to_host = has_high_byte(buf + r[4], r[5]);
+        if (DIALECT == DIALECT_UPB && !is_status && !to_host)
+          to_host = has_high_byte(buf + r.host_off, r.host_len);
       }
       if (to_host) {
         overflow[atomicAdd(&counters[C_OVERFLOW], 1u)] = m;  // at most one per frame: stays below n
-      } else if (r[6] == 0) {
+      } else if (r.ok == OK_ERROR) {
         atomicAdd(&local[is_status ? C_STATUS_ERR : C_PROGRESS_ERR], 1u);
       } else {
-        row.id_off = r[0];
-        row.id_len = r[1];
-        row.status = r[2];
+        row.id_off = r.id_off;
+        row.id_len = r.id_len;
+        row.status = r.status;
         row.flags = F_GROUP | (is_status ? F_STATUS : 0u);
         if (!is_status) {
-          const uint32_t s = static_cast<uint32_t>(r[2]);
+          const uint32_t s = static_cast<uint32_t>(r.status);
           if (s < 64u && ((known_mask >> s) & 1ull)) {
             row.flags |= F_KNOWN;
             atomicAdd(&local[C_HIST + s], 1u);

@@ -1,0 +1,52 @@
+"""The gfx950 extension (``ops/hip/libbeholder_hip.so``) as Python sees it: where it lies, how it is
+loaded, and the argument checks its two callers share (``ops/gpu_decode.py``, ``ops/gpu_fold.py``).
+
+The library is built in-tree by ``beholder_amd._build.build_hip`` (hipcc, gfx950) and loaded with
+ctypes after ``import torch``. torch's HIP runtime has the same soname, so the kernels launch on
+torch's runtime and stream. A missing library raises; there is no CPU fallback behind it.
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+
+LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hip", "libbeholder_hip.so")
+DIALECT_IDS = {"upb": 0, "protobufjs": 1}  # DIALECT_* of hip/telemetry_readers.hpp
+_lib = None
+
+
+def lib() -> ctypes.CDLL:
+    """The HIP extension with both entry points declared (raises if it was not built: no silent
+    fallback)."""
+    global _lib
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise RuntimeError(f"{LIB_PATH} is missing: build it with `python -m beholder_amd.ops.build`")
+        import torch  # noqa: F401  load torch's libamdhip64 first so the kernels share its runtime
+        so = ctypes.CDLL(LIB_PATH)
+        p, i = ctypes.c_void_p, ctypes.c_int
+        so.bh_decode_telemetry.argtypes = [p, p, i, p, p, i]
+        so.bh_decode_telemetry.restype = i
+        so.bh_fold_telemetry.argtypes = [p, p, i, i, ctypes.c_ulonglong, ctypes.c_ulonglong] + [p] * 6 + \
+                                        [ctypes.c_longlong, i, p]
+        so.bh_fold_telemetry.restype = i
+        _lib = so
+    return _lib
+
+
+def check_dialect(dialect: str) -> int:
+    """The kernels' number for ``dialect``; ``ValueError`` for one they do not read."""
+    if dialect not in DIALECT_IDS:
+        raise ValueError(f"unknown dialect {dialect!r} ({'|'.join(DIALECT_IDS)})")
+    return DIALECT_IDS[dialect]
+
+
+def check_device_tensors(buf_dev, offs_dev, n: int) -> None:
+    """What both kernels need of their input: a uint8 ``buf_dev`` and the int32 ``offs_dev`` of
+    ``n + 1`` boundaries, contiguous and on one GPU."""
+    import torch
+    if buf_dev.dtype != torch.uint8 or offs_dev.dtype != torch.int32 or offs_dev.numel() != n + 1:
+        raise ValueError("the kernels need a uint8 buf and int32 offs of n + 1")
+    if not (buf_dev.is_cuda and offs_dev.is_cuda and buf_dev.is_contiguous() and offs_dev.is_contiguous()
+            and buf_dev.device == offs_dev.device):
+        raise ValueError("the kernels need contiguous tensors on one device")

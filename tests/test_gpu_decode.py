@@ -17,10 +17,10 @@ from beholder_amd.bench.generator import Workload
 from beholder_amd.models import proto
 
 np = pytest.importorskip("numpy")  # the probe's host tables are numpy; the service never imports it
-from beholder_amd.ops import gpu_decode as gd  # noqa: E402
+from beholder_amd.ops import gpu_decode as gd, hip_lib  # noqa: E402
+from telemetry_corpus import decode_corpus as _corpus  # noqa: E402
 
 PROGRESS = ops.codec_for(proto.load("api.TelemetryProgress"))
-STATUS = ops.codec_for(proto.load("api.TelemetryStatus"))
 PROGRESS_PBJS = ops.codec_for(proto.load("api.TelemetryProgress"), "protobufjs")
 
 
@@ -89,58 +89,10 @@ def test_layout_guards_and_loud_missing_library(monkeypatch):
                 np.array([0, 3, 3], np.int64)):
         with pytest.raises(ValueError):
             gd.check_layout(len(buf), bad)
-    monkeypatch.setattr(gd, "LIB_PATH", "/nonexistent/libbeholder_hip.so")
-    monkeypatch.setattr(gd, "_lib", None)
+    monkeypatch.setattr(hip_lib, "LIB_PATH", "/nonexistent/libbeholder_hip.so")
+    monkeypatch.setattr(hip_lib, "_lib", None)
     with pytest.raises(RuntimeError, match="missing"):
-        gd.lib()
-
-
-def _corpus(rng: random.Random) -> list:
-    w = Workload(n_media=64, seed=5)
-    bodies = [b for _, b in w.events(3000)]
-    bodies += [STATUS.encode({"mediaId": f"m{i}", "status": i % 7}) for i in range(200)]
-    for _ in range(500):  # truncations, garbage, unknown fields, empty
-        b = rng.choice(bodies)
-        bodies.append(b[:rng.randrange(len(b) + 1)])
-        bodies.append(bytes(rng.getrandbits(8) for _ in range(rng.randrange(0, 30))))
-        bodies.append(b + bytes([0x28, rng.randrange(128), 0x35, 1, 2, 3, 4, 0x39]) + bytes(8))
-    bodies += _malformed(rng)
-    bodies.append(b"")
-    return bodies
-
-
-def _malformed(rng: random.Random) -> list:
-    """Where protobufjs and upb disagree: field 0, known fields with the wrong wire type, strings
-    running past the end (clamped by protobufjs), 5-byte and overlong varints, groups, invalid
-    UTF-8, and a tag varint truncated in its 5th byte."""
-    out = [
-        b"\x00\x05",                         # field 0 (varint): skipped by protobufjs, an error for upb
-        b"\x02\x01x\x0a\x02ok",             # field 0 length-delimited, then mediaId
-        b"\x08\x07",                         # mediaId tagged as a varint: read as a string of length 7
-        b"\x10\x03abc",                      # ... status tagged fine
-        b"\x15\x05\x00\x00\x00",           # status with wire type 5: read as a varint anyway
-        b"\x1a\x2a",                         # progress with wire type 2: varint 42
-        b"\x0a\x7fabc",                      # mediaId of 127 bytes in a 5-byte body: clamped
-        b"\x22\xff\xff\xff\xff\x0fhost",  # host length 2^32-1: clamped
-        b"\x18\xff\xff\xff\xff\xff\x01\x00\x00\x00\x00",  # 10-byte progress varint
-        b"\x18\xff\xff\xff\xff\xff",       # ... truncated inside the unchecked tail
-        b"\x80\x80\x80\x80\x80",           # 5-byte tag with continuation: tail past the end
-        b"\x2b\x08\x01\x2c\x0a\x01z",     # a group (field 5) around a varint, then mediaId
-        b"\x2b\x33\x08\x01\x34\x2c",      # nested groups
-        b"\x2c",                              # end-group with nothing open
-        b"\x2e", b"\x2f\x00",                # wire types 6 / 7
-        b"\x0a\x03\xff\xfe\xfd",           # invalid UTF-8 (protobufjs: U+FFFD)
-        b"\x0a\x02ab\x0a\x01c\x10\x01\x10\x02",  # repeated scalars: last wins
-        b"\x39" + bytes(7),                   # unknown fixed64 one byte short
-        b"\x3d\x01\x02\x03",                # unknown fixed32 one byte short
-    ]
-    for _ in range(400):  # random bodies built from tags of every field number 0-6 and wire type
-        b = bytearray()
-        for _ in range(rng.randrange(1, 6)):
-            b.append((rng.randrange(7) << 3) | rng.randrange(8))
-            b += bytes(rng.getrandbits(8) for _ in range(rng.randrange(0, 6)))
-        out.append(bytes(b))
-    return out
+        hip_lib.lib()
 
 
 def test_pbjs_reference_row_matches_the_service_codec():

@@ -241,7 +241,7 @@ def test_cli_summarise_cpu_round_trips(tmp_path):
 def test_cli_summarise_gpu_without_a_device_names_the_cpu_path(tmp_path, monkeypatch, capsys):
     torch = pytest.importorskip("torch")  # the gpu path's plumbing; the service never imports it
     from beholder_amd import cli
-    from beholder_amd.ops import gpu_decode
+    from beholder_amd.ops import hip_lib
     path = tmp_path / "capture.bin"
     path.write_bytes(Workload(n_media=2, seed=5).framed(10))
     monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
@@ -250,8 +250,8 @@ def test_cli_summarise_gpu_without_a_device_names_the_cpu_path(tmp_path, monkeyp
     assert "--device cpu" in out.err and "no GPU" in out.err and not out.out
     # and with a device but no library
     monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
-    monkeypatch.setattr(gpu_decode, "LIB_PATH", str(tmp_path / "libbeholder_hip.so"))
-    monkeypatch.setattr(gpu_decode, "_lib", None)
+    monkeypatch.setattr(hip_lib, "LIB_PATH", str(tmp_path / "libbeholder_hip.so"))
+    monkeypatch.setattr(hip_lib, "_lib", None)
     assert cli.main(["summarise", str(path), "--device", "gpu"]) != 0
     out = capsys.readouterr()
     assert "--device cpu" in out.err and "missing" in out.err and not out.out
