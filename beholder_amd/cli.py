@@ -7,6 +7,7 @@ config   validate and print the effective config (secrets masked).
 gen      write synthetic framed telemetry to stdout/a file (+ optional media fixture).
 decode   turn a framed stream into NDJSON (debugging).
 summarise  fold a framed stream into its end state: counters, comments, final statuses (``replay``).
+extract  cut a framed stream down to selected frames, a framed stream again (``extract``).
 seed     load a media fixture into a sqlite/postgres store.
 bench    run the BASELINE.json measurement configs (see ``beholder_amd.bench.harness``).
 publish  publish a framed stream to an AMQP broker.
@@ -266,6 +267,75 @@ def cmd_summarise(a: argparse.Namespace) -> int:
     return 0
 
 
+def _topic_byte(text: str) -> int:
+    from .topics import PROGRESS_ID, STATUS_ID
+    named = {"status": STATUS_ID, "progress": PROGRESS_ID}
+    value = named[text] if text in named else int(text)
+    if not 0 <= value <= 255:
+        raise ValueError(f"topic {text!r} is no byte (0-255)")
+    return value
+
+
+def _status_number(text: str) -> int:
+    from . import replay
+    by_name = {name.upper(): number for number, name in replay.status_names().items()}
+    if text.upper() in by_name:
+        return by_name[text.upper()]
+    try:
+        return int(text)
+    except ValueError:
+        raise ValueError(f"unknown status {text!r} ({'|'.join(sorted(by_name))} or a number 0-63)") from None
+
+
+def cmd_extract(a: argparse.Namespace) -> int:
+    """Cut a framed stream down to the selected frames (``beholder_amd.extract``)."""
+    from . import extract
+    try:
+        media = None
+        if a.media or a.media_file:
+            media = set(a.media or ())
+            for name in a.media_file or ():
+                with open(name, "r", encoding="utf-8", newline="") as f:
+                    media.update(line.rstrip("\r\n") for line in f)
+        selector = extract.Selector(
+            topics={_topic_byte(t) for t in a.topic} if a.topic else None,
+            outcomes=set(a.outcome) if a.outcome else None, media=media,
+            statuses={_status_number(s) for s in a.status} if a.status else None,
+            unknown_status=a.unknown_status, invert=a.invert)
+    except (ValueError, OSError) as e:
+        print(f"beholder: {e}", file=sys.stderr)
+        return 2
+    if a.device == "gpu":
+        try:
+            import torch
+
+            from .ops import gpu_extract, hip_lib  # noqa: F401  gpu_extract: its imports fail here, not mid-run
+            if not torch.cuda.is_available():
+                raise RuntimeError("no GPU is visible")
+            hip_lib.lib()
+        except (ImportError, RuntimeError, OSError) as e:
+            print(f"beholder: --device gpu is not available ({e}); use --device cpu", file=sys.stderr)
+            return 1
+    source = a.input if a.input else sys.stdin.buffer
+    out = sys.stdout.buffer if a.out == "-" else open(a.out, "wb")
+    indices = open(a.indices, "w", encoding="ascii") if a.indices else None
+    try:
+        counts = extract.extract_file(source, out, selector, device=a.device, dialect=a.dialect,
+                                      chunk_bytes=a.chunk_bytes, indices_out=indices)
+    except ValueError as e:  # broken framing: what was written so far is whole frames
+        print(f"beholder: {e}", file=sys.stderr)
+        return 1
+    finally:
+        if indices is not None:
+            indices.close()
+        if a.out == "-":
+            out.flush()
+        else:
+            out.close()
+    print(json.dumps(counts), file=sys.stderr)
+    return 0
+
+
 def cmd_seed(a: argparse.Namespace) -> int:
     from .store import open_store
 
@@ -354,6 +424,28 @@ def build_parser() -> argparse.ArgumentParser:
     z.add_argument("--media-fixture", help="JSON list of media rows: also print the prediction for them")
     z.add_argument("--chunk-bytes", type=int, default=256 << 20, help="fold the input in pieces of this size")
     z.set_defaults(fn=cmd_summarise)
+
+    x = sub.add_parser("extract", help="framed stream -> the selected frames, a framed stream again",
+                       description="Keep the frames that meet every given condition (none: all frames); "
+                                   "the counts go to stderr as one JSON line.")
+    x.add_argument("input", nargs="?")
+    x.add_argument("-o", "--out", required=True, help="output file ('-' for stdout)")
+    x.add_argument("--topic", action="append", metavar="status|progress|N", help="topic byte; repeatable")
+    x.add_argument("--outcome", action="append", choices=["decoded", "error", "other"],
+                   help="decoded, error (the topic's codec raises) or other (neither topic); repeatable")
+    x.add_argument("--media", action="append", metavar="ID", help="mediaId of a decoded frame; repeatable")
+    x.add_argument("--media-file", action="append", metavar="FILE", help="mediaIds, one per line (an empty line is the empty id); repeatable")
+    x.add_argument("--status", action="append", metavar="NAME|N",
+                   help="status of a decoded frame, a TelemetryStatusEntry name or a number 0-63; repeatable")
+    x.add_argument("--unknown-status", action="store_true",
+                   help="a decoded frame whose status is no TelemetryStatusEntry number (quirk Q6)")
+    x.add_argument("--invert", action="store_true", help="keep exactly the frames the rest rejects")
+    x.add_argument("--device", choices=["cpu", "gpu"], default="cpu",
+                   help="cpu: the definition, runs anywhere; gpu: the gfx950 select kernels")
+    x.add_argument("--dialect", choices=["protobufjs", "upb"], default="protobufjs")
+    x.add_argument("--chunk-bytes", type=int, default=256 << 20, help="cut the input in pieces of this size")
+    x.add_argument("--indices", metavar="FILE", help="write the kept frames' input indices here, one per line")
+    x.set_defaults(fn=cmd_extract)
 
     s = sub.add_parser("seed", help="load a media fixture into a store")
     s.add_argument("fixture")

@@ -1,5 +1,6 @@
 """The gfx950 extension (``ops/hip/libbeholder_hip.so``) as Python sees it: where it lies, how it is
-loaded, and the argument checks its two callers share (``ops/gpu_decode.py``, ``ops/gpu_fold.py``).
+loaded, and the argument checks its callers share (``ops/gpu_decode.py``, ``ops/gpu_fold.py``,
+``ops/gpu_extract.py``).
 
 The library is built in-tree by ``beholder_amd._build.build_hip`` (hipcc, gfx950) and loaded with
 ctypes after ``import torch``. torch's HIP runtime has the same soname, so the kernels launch on
@@ -16,7 +17,7 @@ _lib = None
 
 
 def lib() -> ctypes.CDLL:
-    """The HIP extension with both entry points declared (raises if it was not built: no silent
+    """The HIP extension with its entry points declared (raises if it was not built: no silent
     fallback)."""
     global _lib
     if _lib is None:
@@ -30,6 +31,13 @@ def lib() -> ctypes.CDLL:
         so.bh_fold_telemetry.argtypes = [p, p, i, i, ctypes.c_ulonglong, ctypes.c_ulonglong] + [p] * 6 + \
                                         [ctypes.c_longlong, i, p]
         so.bh_fold_telemetry.restype = i
+        # telemetry_select.hip (ops/gpu_extract.py): mark, scan, gather
+        so.bh_select_mark.argtypes = [p, p, i, i] + [p] * 7
+        so.bh_select_mark.restype = i
+        so.bh_select_scan.argtypes = [p, i] + [p] * 6
+        so.bh_select_scan.restype = i
+        so.bh_select_gather.argtypes = [p, p, i, p, p, p, p, i, i, p, i, p]
+        so.bh_select_gather.restype = i
         _lib = so
     return _lib
 
