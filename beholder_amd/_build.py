@@ -7,8 +7,9 @@ codec, deliveries, histograms) is C++ — see ``csrc/``. The service has no
 device kernels in its event path (the reference has none), so the runtime is a
 host build with the system C++ compiler. ``build_hip`` compiles the batched-decode kernel that
 ``scripts/gpu_offload_probe.py`` measures against it (``ops/gpu_decode.py``), the stream-fold
-kernels behind ``summarise --device gpu`` (``ops/gpu_fold.py``) and the select kernels behind
-``extract --device gpu`` (``ops/gpu_extract.py``) into one library.
+kernels behind ``summarise --device gpu`` (``ops/gpu_fold.py``), the select kernels behind
+``extract --device gpu`` (``ops/gpu_extract.py``) and the coalesce kernels behind
+``coalesce --device gpu`` (``ops/gpu_coalesce.py``) into one library.
 ``__graft_entry__.build()`` calls both.
 
 The HIP library is optional for the service: ``main`` builds it only when ``hipcc`` is present

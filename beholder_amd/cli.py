@@ -8,6 +8,7 @@ gen      write synthetic framed telemetry to stdout/a file (+ optional media fix
 decode   turn a framed stream into NDJSON (debugging).
 summarise  fold a framed stream into its end state: counters, comments, final statuses (``replay``).
 extract  cut a framed stream down to selected frames, a framed stream again (``extract``).
+coalesce  cut a framed stream down to the frames that set its end state, a framed stream again (``coalesce``).
 seed     load a media fixture into a sqlite/postgres store.
 bench    run the BASELINE.json measurement configs (see ``beholder_amd.bench.harness``).
 publish  publish a framed stream to an AMQP broker.
@@ -336,6 +337,62 @@ def cmd_extract(a: argparse.Namespace) -> int:
     return 0
 
 
+class _LazyOutput:
+    """The output file of ``coalesce``, opened at the first write or at ``finish``: a run that fails
+    before it has anything to write leaves no file behind."""
+
+    def __init__(self, name: str, text: bool = False):
+        self.name = name
+        self.text = text
+        self.file = None
+
+    def write(self, data) -> int:
+        if self.file is None:
+            if self.text:
+                self.file = open(self.name, "w", encoding="ascii")
+            else:
+                self.file = sys.stdout.buffer if self.name == "-" else open(self.name, "wb")
+        return self.file.write(data)
+
+    def finish(self) -> None:
+        self.write("" if self.text else b"")
+        if self.name == "-" and not self.text:
+            self.file.flush()
+        else:
+            self.file.close()
+
+
+def cmd_coalesce(a: argparse.Namespace) -> int:
+    """Cut a framed stream down to the frames that set its end state (``beholder_amd.coalesce``)."""
+    from . import coalesce
+    policy = coalesce.Policy(status=a.status, progress=a.progress, undecoded=a.undecoded)  # argparse checked the values
+    if a.device == "gpu":
+        try:
+            import torch
+
+            from .ops import gpu_coalesce, hip_lib  # noqa: F401  gpu_coalesce: its imports fail here, not mid-run
+            if not torch.cuda.is_available():
+                raise RuntimeError("no GPU is visible")
+            hip_lib.lib()
+        except (ImportError, RuntimeError, OSError) as e:
+            print(f"beholder: --device gpu is not available ({e}); use --device cpu", file=sys.stderr)
+            return 1
+    source = a.input if a.input else sys.stdin.buffer
+    out = _LazyOutput(a.out)
+    indices = _LazyOutput(a.indices, text=True) if a.indices else None
+    try:
+        counts = coalesce.coalesce_file(source, out, policy, device=a.device, dialect=a.dialect,
+                                        chunk_bytes=a.chunk_bytes, indices_out=indices)
+    except ValueError as e:  # broken framing: nothing was written
+        print(f"beholder: {e}", file=sys.stderr)
+        return 1
+    out.finish()
+    if indices is not None:
+        indices.finish()
+    print(json.dumps(counts), file=sys.stderr)
+    return 0
+
+
 def cmd_seed(a: argparse.Namespace) -> int:
     from .store import open_store
 
@@ -446,6 +503,26 @@ def build_parser() -> argparse.ArgumentParser:
     x.add_argument("--chunk-bytes", type=int, default=256 << 20, help="cut the input in pieces of this size")
     x.add_argument("--indices", metavar="FILE", help="write the kept frames' input indices here, one per line")
     x.set_defaults(fn=cmd_extract)
+
+    o = sub.add_parser("coalesce", help="framed stream -> the frames that set its end state, a framed stream again",
+                       description="Keep, per key, the last frame only: by default the last status event and the "
+                                   "last progress event of every mediaId, and every frame that is neither. "
+                                   "The counts go to stderr as one JSON line.")
+    o.add_argument("input", nargs="?")
+    o.add_argument("-o", "--out", required=True, help="output file ('-' for stdout)")
+    o.add_argument("--status", choices=["last", "all"], default="last",
+                   help="decoded status events: the last per mediaId, or all of them")
+    o.add_argument("--progress", choices=["last", "per-status", "all", "none"], default="last",
+                   help="decoded progress events: the last per mediaId, the last per mediaId and status number, "
+                        "all (keeps beholder_progress_updates_total whole) or none")
+    o.add_argument("--undecoded", choices=["keep", "drop"], default="keep",
+                   help="frames that fail to decode or carry another topic byte")
+    o.add_argument("--device", choices=["cpu", "gpu"], default="cpu",
+                   help="cpu: the definition, runs anywhere; gpu: the gfx950 coalesce kernels")
+    o.add_argument("--dialect", choices=["protobufjs", "upb"], default="protobufjs")
+    o.add_argument("--chunk-bytes", type=int, default=256 << 20, help="cut the input in pieces of this size")
+    o.add_argument("--indices", metavar="FILE", help="write the kept frames' input indices here, one per line")
+    o.set_defaults(fn=cmd_coalesce)
 
     s = sub.add_parser("seed", help="load a media fixture into a store")
     s.add_argument("fixture")

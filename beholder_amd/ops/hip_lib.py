@@ -1,6 +1,6 @@
 """The gfx950 extension (``ops/hip/libbeholder_hip.so``) as Python sees it: where it lies, how it is
 loaded, and the argument checks its callers share (``ops/gpu_decode.py``, ``ops/gpu_fold.py``,
-``ops/gpu_extract.py``).
+``ops/gpu_extract.py``, ``ops/gpu_coalesce.py``).
 
 The library is built in-tree by ``beholder_amd._build.build_hip`` (hipcc, gfx950) and loaded with
 ctypes after ``import torch``. torch's HIP runtime has the same soname, so the kernels launch on
@@ -38,6 +38,9 @@ def lib() -> ctypes.CDLL:
         so.bh_select_scan.restype = i
         so.bh_select_gather.argtypes = [p, p, i, p, p, p, p, i, i, p, i, p]
         so.bh_select_gather.restype = i
+        # telemetry_coalesce.hip (ops/gpu_coalesce.py): classify, claim, mark
+        so.bh_coalesce_mark.argtypes = [p, p, i, i] + [p] * 9 + [i, p]
+        so.bh_coalesce_mark.restype = i
         _lib = so
     return _lib
 
