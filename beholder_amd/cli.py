@@ -9,6 +9,7 @@ decode   turn a framed stream into NDJSON (debugging).
 summarise  fold a framed stream into its end state: counters, comments, final statuses (``replay``).
 extract  cut a framed stream down to selected frames, a framed stream again (``extract``).
 coalesce  cut a framed stream down to the frames that set its end state, a framed stream again (``coalesce``).
+shard    split a framed stream by media into N framed streams, each media's events in order (``shard``).
 seed     load a media fixture into a sqlite/postgres store.
 bench    run the BASELINE.json measurement configs (see ``beholder_amd.bench.harness``).
 publish  publish a framed stream to an AMQP broker.
@@ -393,6 +394,50 @@ def cmd_coalesce(a: argparse.Namespace) -> int:
     return 0
 
 
+def cmd_shard(a: argparse.Namespace) -> int:
+    """Split a framed stream by media into N framed streams (``beholder_amd.shard``)."""
+    from . import shard
+    try:
+        policy = shard.Policy(shards=a.shards, undecoded=a.undecoded)
+        for pattern in (a.out, a.indices):
+            if pattern is not None and "{}" not in pattern:
+                raise ValueError(f"the pattern {pattern!r} needs a '{{}}' for the shard number")
+    except ValueError as e:
+        print(f"beholder: {e}", file=sys.stderr)
+        return 2
+    if a.device == "gpu":
+        try:
+            import torch
+
+            from .ops import gpu_shard, hip_lib  # noqa: F401  gpu_shard: its imports fail here, not mid-run
+            if not torch.cuda.is_available():
+                raise RuntimeError("no GPU is visible")
+            hip_lib.lib()
+        except (ImportError, RuntimeError, OSError) as e:
+            print(f"beholder: --device gpu is not available ({e}); use --device cpu", file=sys.stderr)
+            return 1
+    source = a.input if a.input else sys.stdin.buffer
+    outs = [_LazyOutput(a.out.replace("{}", str(s))) for s in range(policy.shards)]
+    indices = [_LazyOutput(a.indices.replace("{}", str(s)), text=True) for s in range(policy.shards)] \
+        if a.indices else None
+    failed = None
+    try:
+        counts = shard.shard_file(source, outs, policy, device=a.device, dialect=a.dialect,
+                                  chunk_bytes=a.chunk_bytes, indices_outs=indices)
+    except ValueError as e:  # broken framing: what was written so far is whole frames
+        failed = e
+    for f in outs + (indices or []):
+        if failed is None:
+            f.finish()  # every shard gets a file, an empty one included
+        elif f.file is not None:
+            f.file.close()
+    if failed is not None:
+        print(f"beholder: {failed}", file=sys.stderr)
+        return 1
+    print(json.dumps(counts), file=sys.stderr)
+    return 0
+
+
 def cmd_seed(a: argparse.Namespace) -> int:
     from .store import open_store
 
@@ -523,6 +568,24 @@ def build_parser() -> argparse.ArgumentParser:
     o.add_argument("--chunk-bytes", type=int, default=256 << 20, help="cut the input in pieces of this size")
     o.add_argument("--indices", metavar="FILE", help="write the kept frames' input indices here, one per line")
     o.set_defaults(fn=cmd_coalesce)
+
+    h = sub.add_parser("shard", help="framed stream -> N framed streams, split by media, for parallel replay in order",
+                       description="Every mediaId's events go to one shard, in their original order; the shard "
+                                   "is a function of the decoded mediaId and N alone. "
+                                   "The counts go to stderr as one JSON line.")
+    h.add_argument("input", nargs="?")
+    h.add_argument("--shards", type=int, required=True, metavar="N", help="how many streams, 1-256")
+    h.add_argument("-o", "--out", required=True, metavar="PATTERN",
+                   help="output files; '{}' becomes the shard number ('dlq-{}.bin')")
+    h.add_argument("--undecoded", choices=["first", "drop"], default="first",
+                   help="frames that fail to decode or carry another topic byte: to shard 0, or nowhere")
+    h.add_argument("--device", choices=["cpu", "gpu"], default="cpu",
+                   help="cpu: the definition, runs anywhere; gpu: the gfx950 shard kernels")
+    h.add_argument("--dialect", choices=["protobufjs", "upb"], default="protobufjs")
+    h.add_argument("--chunk-bytes", type=int, default=256 << 20, help="cut the input in pieces of this size")
+    h.add_argument("--indices", metavar="PATTERN",
+                   help="write each shard's input indices to these files, one per line; '{}' as in -o")
+    h.set_defaults(fn=cmd_shard)
 
     s = sub.add_parser("seed", help="load a media fixture into a store")
     s.add_argument("fixture")

@@ -35,6 +35,7 @@
 // Visibility is the fold's rule: within a launch workgroups meet only in atomics (the overflow
 // cursor); every plain load reads what an earlier launch or the host wrote. No kernel waits for
 // another workgroup, which is why the scan is three launches and not a single look-back pass.
+#include "block_scan.hpp"
 #include "telemetry_select.hpp"
 
 namespace {
@@ -62,33 +63,12 @@ __device__ __forceinline__ uint64_t packed(int32_t len) {
   return len > 0 ? (1ull << 32) | static_cast<uint32_t>(len) : 0ull;
 }
 
-// Inclusive scan of one value per thread over the block of BLOCK threads; `total` is the block's
-// sum. wave_sums holds one entry per wave. Every thread of the block must call it.
-__device__ __forceinline__ uint64_t block_scan(uint64_t x, uint64_t* wave_sums, uint64_t& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint64_t y = __shfl_up(x, d);
-    if (lane >= d) x += y;
-  }
-  __syncthreads();  // the previous call's readers are done with wave_sums
-  if (lane == 63) wave_sums[wave] = x;
-  __syncthreads();
-  uint64_t before = 0, all = 0;
-  for (int w = 0; w < BLOCK / 64; ++w) {
-    const uint64_t t = wave_sums[w];
-    if (w < wave) before += t;
-    all += t;
-  }
-  total = all;
-  return x + before;
-}
-
 __global__ __launch_bounds__(BLOCK) void scan_reduce(const int32_t* __restrict__ keep_len, int n,
                                                      uint64_t* __restrict__ totals) {
   __shared__ uint64_t wave_sums[BLOCK / 64];
   const int m = blockIdx.x * BLOCK + threadIdx.x;
   uint64_t total;
-  block_scan(m < n ? packed(keep_len[m]) : 0ull, wave_sums, total);
+  block_scan<BLOCK>(m < n ? packed(keep_len[m]) : 0ull, wave_sums, total);
   if (threadIdx.x == 0) totals[blockIdx.x] = total;
 }
 
@@ -101,7 +81,7 @@ __global__ __launch_bounds__(BLOCK) void scan_totals(const uint64_t* __restrict_
     const int b = tile + threadIdx.x;
     const uint64_t x = b < blocks ? totals[b] : 0ull;
     uint64_t total;
-    const uint64_t incl = block_scan(x, wave_sums, total);
+    const uint64_t incl = block_scan<BLOCK>(x, wave_sums, total);
     if (b < blocks) base[b] = carry + incl - x;
     carry += total;
   }
@@ -115,7 +95,7 @@ __global__ __launch_bounds__(BLOCK) void scan_apply(const int32_t* __restrict__ 
   const int m = blockIdx.x * BLOCK + threadIdx.x;
   const uint64_t x = m < n ? packed(keep_len[m]) : 0ull;
   uint64_t total;
-  const uint64_t incl = block_scan(x, wave_sums, total) + base[blockIdx.x];
+  const uint64_t incl = block_scan<BLOCK>(x, wave_sums, total) + base[blockIdx.x];
   if (m >= n) return;
   const uint64_t excl = incl - x;
   pos[m] = excl;
