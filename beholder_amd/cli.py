@@ -8,6 +8,7 @@ gen      write synthetic framed telemetry to stdout/a file (+ optional media fix
 decode   turn a framed stream into NDJSON (debugging).
 summarise  fold a framed stream into its end state: counters, comments, final statuses (``replay``).
 extract  cut a framed stream down to selected frames, a framed stream again (``extract``).
+dedupe   drop the byte-identical repeat frames of a framed stream, a framed stream again (``dedupe``).
 coalesce  cut a framed stream down to the frames that set its end state, a framed stream again (``coalesce``).
 shard    split a framed stream by media into N framed streams, each media's events in order (``shard``).
 seed     load a media fixture into a sqlite/postgres store.
@@ -394,6 +395,51 @@ def cmd_coalesce(a: argparse.Namespace) -> int:
     return 0
 
 
+def cmd_dedupe(a: argparse.Namespace) -> int:
+    """Drop the byte-identical repeat frames of a framed stream (``beholder_amd.dedupe``)."""
+    from . import dedupe
+    try:
+        policy = dedupe.Policy(keep=a.keep, topics={_topic_byte(t) for t in a.topic} if a.topic else None)
+    except ValueError as e:
+        print(f"beholder: {e}", file=sys.stderr)
+        return 2
+    if a.device == "gpu":
+        try:
+            import torch
+
+            from .ops import gpu_dedupe, hip_lib  # noqa: F401  gpu_dedupe: its imports fail here, not mid-run
+            if not torch.cuda.is_available():
+                raise RuntimeError("no GPU is visible")
+            hip_lib.lib()
+        except (ImportError, RuntimeError, OSError) as e:
+            print(f"beholder: --device gpu is not available ({e}); use --device cpu", file=sys.stderr)
+            return 1
+    source = a.input if a.input else sys.stdin.buffer
+    out = _LazyOutput(a.out)
+    indices = _LazyOutput(a.indices, text=True) if a.indices else None
+    failed = None
+    try:
+        counts = dedupe.dedupe_file(source, out, policy, device=a.device, chunk_bytes=a.chunk_bytes,
+                                    indices_out=indices)
+    except ValueError as e:  # broken framing: nothing was written (last), or whole frames only (first)
+        failed = e
+    for f in (out, indices):
+        if f is None:
+            continue
+        if failed is None:
+            f.finish()
+        elif f.file is not None:
+            if f.name == "-" and not f.text:
+                f.file.flush()
+            else:
+                f.file.close()
+    if failed is not None:
+        print(f"beholder: {failed}", file=sys.stderr)
+        return 1
+    print(json.dumps(counts), file=sys.stderr)
+    return 0
+
+
 def cmd_shard(a: argparse.Namespace) -> int:
     """Split a framed stream by media into N framed streams (``beholder_amd.shard``)."""
     from . import shard
@@ -548,6 +594,22 @@ def build_parser() -> argparse.ArgumentParser:
     x.add_argument("--chunk-bytes", type=int, default=256 << 20, help="cut the input in pieces of this size")
     x.add_argument("--indices", metavar="FILE", help="write the kept frames' input indices here, one per line")
     x.set_defaults(fn=cmd_extract)
+
+    u = sub.add_parser("dedupe", help="framed stream -> the same without byte-identical repeat frames",
+                       description="Keep one frame of every distinct content (topic byte and body), by default "
+                                   "the last, which is the one that is safe to replay; nothing is decoded. "
+                                   "The counts go to stderr as one JSON line.")
+    u.add_argument("input", nargs="?")
+    u.add_argument("-o", "--out", required=True, help="output file ('-' for stdout)")
+    u.add_argument("--keep", choices=["last", "first"], default="last",
+                   help="which occurrence of a content survives; 'first' can end a replay on a stale status")
+    u.add_argument("--topic", action="append", metavar="status|progress|N",
+                   help="only frames of this topic byte take part, the others are kept as they are; repeatable")
+    u.add_argument("--device", choices=["cpu", "gpu"], default="cpu",
+                   help="cpu: the definition, runs anywhere; gpu: the gfx950 dedupe kernels")
+    u.add_argument("--chunk-bytes", type=int, default=256 << 20, help="cut the input in pieces of this size")
+    u.add_argument("--indices", metavar="FILE", help="write the kept frames' input indices here, one per line")
+    u.set_defaults(fn=cmd_dedupe)
 
     o = sub.add_parser("coalesce", help="framed stream -> the frames that set its end state, a framed stream again",
                        description="Keep, per key, the last frame only: by default the last status event and the "

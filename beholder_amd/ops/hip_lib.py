@@ -1,6 +1,6 @@
 """The gfx950 extension (``ops/hip/libbeholder_hip.so``) as Python sees it: where it lies, how it is
 loaded, and the argument checks its callers share (``ops/gpu_decode.py``, ``ops/gpu_fold.py``,
-``ops/gpu_extract.py``, ``ops/gpu_coalesce.py``, ``ops/gpu_shard.py``).
+``ops/gpu_extract.py``, ``ops/gpu_coalesce.py``, ``ops/gpu_shard.py``, ``ops/gpu_dedupe.py``).
 
 The library is built in-tree by ``beholder_amd._build.build_hip`` (hipcc, gfx950) and loaded with
 ctypes after ``import torch``. torch's HIP runtime has the same soname, so the kernels launch on
@@ -46,6 +46,9 @@ def lib() -> ctypes.CDLL:
         so.bh_shard_route.restype = i
         so.bh_shard_partition.argtypes = [p, p, i, i] + [p] * 6 + [i, i, p]
         so.bh_shard_partition.restype = i
+        # telemetry_dedupe.hip (ops/gpu_dedupe.py): hash, claim, mark
+        so.bh_dedupe_mark.argtypes = [p, p, i] + [p] * 8 + [i, p]
+        so.bh_dedupe_mark.restype = i
         _lib = so
     return _lib
 
