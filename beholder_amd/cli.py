@@ -7,6 +7,7 @@ config   validate and print the effective config (secrets masked).
 gen      write synthetic framed telemetry to stdout/a file (+ optional media fixture).
 decode   turn a framed stream into NDJSON (debugging).
 summarise  fold a framed stream into its end state: counters, comments, final statuses (``replay``).
+transitions  count a framed stream's per-media status moves: the transition matrix, changes, repeats (``transitions``).
 extract  cut a framed stream down to selected frames, a framed stream again (``extract``).
 dedupe   drop the byte-identical repeat frames of a framed stream, a framed stream again (``dedupe``).
 coalesce  cut a framed stream down to the frames that set its end state, a framed stream again (``coalesce``).
@@ -266,6 +267,35 @@ def cmd_summarise(a: argparse.Namespace) -> int:
     out = {"summary": summary.to_json()}
     if a.media_fixture:
         out["prediction"] = summary.apply(_load_fixture(a.media_fixture))
+    print(json.dumps(out))
+    return 0
+
+
+def cmd_transitions(a: argparse.Namespace) -> int:
+    """How the media of this stream got where they end: their status moves (``beholder_amd.transitions``)."""
+    import io
+
+    from . import transitions
+    if a.device == "gpu":
+        try:
+            import torch
+
+            from .ops import gpu_transitions, hip_lib  # noqa: F401  gpu_transitions: its imports fail here, not mid-run
+            if not torch.cuda.is_available():
+                raise RuntimeError("no GPU is visible")
+            hip_lib.lib()
+        except (ImportError, RuntimeError, OSError) as e:
+            print(f"beholder: --device gpu is not available ({e}); use --device cpu", file=sys.stderr)
+            return 1
+    try:
+        source = a.input if a.input else io.BytesIO(sys.stdin.buffer.read())
+        result, host_frames = transitions.transitions_file(source, device=a.device, dialect=a.dialect,
+                                                           chunk_bytes=a.chunk_bytes)
+    except ValueError as e:
+        print(f"beholder: {e}", file=sys.stderr)
+        return 1
+    out = result.to_json(per_media=a.per_media)
+    out["host_frames"] = host_frames
     print(json.dumps(out))
     return 0
 
@@ -572,6 +602,18 @@ def build_parser() -> argparse.ArgumentParser:
     z.add_argument("--media-fixture", help="JSON list of media rows: also print the prediction for them")
     z.add_argument("--chunk-bytes", type=int, default=256 << 20, help="fold the input in pieces of this size")
     z.set_defaults(fn=cmd_summarise)
+
+    t = sub.add_parser("transitions", help="framed stream -> its per-media status moves (JSON)",
+                       description="Count, over every media's status events in stream order, the moves between "
+                                   "status classes: the transition matrix, changes, repeats, and the classes "
+                                   "the media start and end on. Prints one JSON object.")
+    t.add_argument("input", nargs="?")
+    t.add_argument("--device", choices=["cpu", "gpu"], default="cpu",
+                   help="cpu: the definition, runs anywhere; gpu: the gfx950 transitions kernels")
+    t.add_argument("--dialect", choices=["protobufjs", "upb"], default="protobufjs")
+    t.add_argument("--chunk-bytes", type=int, default=256 << 20, help="read the input in pieces of this size")
+    t.add_argument("--per-media", action="store_true", help="also print one row per mediaId")
+    t.set_defaults(fn=cmd_transitions)
 
     x = sub.add_parser("extract", help="framed stream -> the selected frames, a framed stream again",
                        description="Keep the frames that meet every given condition (none: all frames); "

@@ -1,6 +1,7 @@
 """The gfx950 extension (``ops/hip/libbeholder_hip.so``) as Python sees it: where it lies, how it is
 loaded, and the argument checks its callers share (``ops/gpu_decode.py``, ``ops/gpu_fold.py``,
-``ops/gpu_extract.py``, ``ops/gpu_coalesce.py``, ``ops/gpu_shard.py``, ``ops/gpu_dedupe.py``).
+``ops/gpu_extract.py``, ``ops/gpu_coalesce.py``, ``ops/gpu_shard.py``, ``ops/gpu_dedupe.py``,
+``ops/gpu_transitions.py``).
 
 The library is built in-tree by ``beholder_amd._build.build_hip`` (hipcc, gfx950) and loaded with
 ctypes after ``import torch``. torch's HIP runtime has the same soname, so the kernels launch on
@@ -49,6 +50,17 @@ def lib() -> ctypes.CDLL:
         # telemetry_dedupe.hip (ops/gpu_dedupe.py): hash, claim, mark
         so.bh_dedupe_mark.argtypes = [p, p, i] + [p] * 8 + [i, p]
         so.bh_dedupe_mark.restype = i
+        # telemetry_transitions.hip (ops/gpu_transitions.py): classify, claim, compact, sort pass, pairs
+        so.bh_transitions_classify.argtypes = [p, p, i, i] + [p] * 5
+        so.bh_transitions_classify.restype = i
+        so.bh_transitions_claim.argtypes = [p, p, i, ctypes.c_ulonglong, p, p, p, ctypes.c_longlong, p]
+        so.bh_transitions_claim.restype = i
+        so.bh_transitions_compact.argtypes = [p] * 4 + [i, p, p, p]
+        so.bh_transitions_compact.restype = i
+        so.bh_transitions_sort_pass.argtypes = [p, p, i, i] + [p] * 4 + [i, p]
+        so.bh_transitions_sort_pass.restype = i
+        so.bh_transitions_pairs.argtypes = [p, p, i, i, ctypes.c_ulonglong] + [p] * 7
+        so.bh_transitions_pairs.restype = i
         _lib = so
     return _lib
 
