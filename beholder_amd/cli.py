@@ -10,6 +10,7 @@ summarise  fold a framed stream into its end state: counters, comments, final st
 transitions  count a framed stream's per-media status moves: the transition matrix, changes, repeats (``transitions``).
 extract  cut a framed stream down to selected frames, a framed stream again (``extract``).
 dedupe   drop the byte-identical repeat frames of a framed stream, a framed stream again (``dedupe``).
+thin     drop the progress events that repeat their media's step, a framed stream again (``thin``).
 coalesce  cut a framed stream down to the frames that set its end state, a framed stream again (``coalesce``).
 shard    split a framed stream by media into N framed streams, each media's events in order (``shard``).
 seed     load a media fixture into a sqlite/postgres store.
@@ -470,6 +471,51 @@ def cmd_dedupe(a: argparse.Namespace) -> int:
     return 0
 
 
+def cmd_thin(a: argparse.Namespace) -> int:
+    """Drop the progress events that repeat their media's step (``beholder_amd.thin``)."""
+    from . import thin
+    try:
+        policy = thin.Policy(step=a.step, keep=a.keep)
+    except ValueError as e:
+        print(f"beholder: {e}", file=sys.stderr)
+        return 2
+    if a.device == "gpu":
+        try:
+            import torch
+
+            from .ops import gpu_thin, hip_lib  # noqa: F401  gpu_thin: its imports fail here, not mid-run
+            if not torch.cuda.is_available():
+                raise RuntimeError("no GPU is visible")
+            hip_lib.lib()
+        except (ImportError, RuntimeError, OSError) as e:
+            print(f"beholder: --device gpu is not available ({e}); use --device cpu", file=sys.stderr)
+            return 1
+    source = a.input if a.input else sys.stdin.buffer
+    out = _LazyOutput(a.out)
+    indices = _LazyOutput(a.indices, text=True) if a.indices else None
+    failed = None
+    try:
+        counts = thin.thin_file(source, out, policy, device=a.device, dialect=a.dialect, chunk_bytes=a.chunk_bytes,
+                                indices_out=indices)
+    except ValueError as e:  # broken framing: nothing was written (last), or whole frames only (first)
+        failed = e
+    for f in (out, indices):
+        if f is None:
+            continue
+        if failed is None:
+            f.finish()
+        elif f.file is not None:
+            if f.name == "-" and not f.text:
+                f.file.flush()
+            else:
+                f.file.close()
+    if failed is not None:
+        print(f"beholder: {failed}", file=sys.stderr)
+        return 1
+    print(json.dumps(counts), file=sys.stderr)
+    return 0
+
+
 def cmd_shard(a: argparse.Namespace) -> int:
     """Split a framed stream by media into N framed streams (``beholder_amd.shard``)."""
     from . import shard
@@ -652,6 +698,23 @@ def build_parser() -> argparse.ArgumentParser:
     u.add_argument("--chunk-bytes", type=int, default=256 << 20, help="cut the input in pieces of this size")
     u.add_argument("--indices", metavar="FILE", help="write the kept frames' input indices here, one per line")
     u.set_defaults(fn=cmd_dedupe)
+
+    h = sub.add_parser("thin", help="framed stream -> the same without the progress events that repeat their step",
+                       description="Keep a media's progress history only where it moves: of neighbouring progress "
+                                   "events of one mediaId with the same status and the same progress // STEP, one "
+                                   "survives, by default the last. Every other frame is kept as it is. "
+                                   "The counts go to stderr as one JSON line.")
+    h.add_argument("input", nargs="?")
+    h.add_argument("-o", "--out", required=True, help="output file ('-' for stdout)")
+    h.add_argument("--step", type=int, default=10, help="the width of a step in percentage points (1..2^31-1)")
+    h.add_argument("--keep", choices=["last", "first"], default="last",
+                   help="which event of a stretch of one step survives; 'last' keeps every stage's last event")
+    h.add_argument("--device", choices=["cpu", "gpu"], default="cpu",
+                   help="cpu: the definition, runs anywhere; gpu: the gfx950 thin kernels")
+    h.add_argument("--dialect", choices=["protobufjs", "upb"], default="protobufjs")
+    h.add_argument("--chunk-bytes", type=int, default=256 << 20, help="cut the input in pieces of this size")
+    h.add_argument("--indices", metavar="FILE", help="write the kept frames' input indices here, one per line")
+    h.set_defaults(fn=cmd_thin)
 
     o = sub.add_parser("coalesce", help="framed stream -> the frames that set its end state, a framed stream again",
                        description="Keep, per key, the last frame only: by default the last status event and the "

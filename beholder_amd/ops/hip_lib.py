@@ -1,7 +1,7 @@
 """The gfx950 extension (``ops/hip/libbeholder_hip.so``) as Python sees it: where it lies, how it is
 loaded, and the argument checks its callers share (``ops/gpu_decode.py``, ``ops/gpu_fold.py``,
 ``ops/gpu_extract.py``, ``ops/gpu_coalesce.py``, ``ops/gpu_shard.py``, ``ops/gpu_dedupe.py``,
-``ops/gpu_transitions.py``).
+``ops/gpu_transitions.py``, ``ops/gpu_thin.py``).
 
 The library is built in-tree by ``beholder_amd._build.build_hip`` (hipcc, gfx950) and loaded with
 ctypes after ``import torch``. torch's HIP runtime has the same soname, so the kernels launch on
@@ -61,6 +61,11 @@ def lib() -> ctypes.CDLL:
         so.bh_transitions_sort_pass.restype = i
         so.bh_transitions_pairs.argtypes = [p, p, i, i, ctypes.c_ulonglong] + [p] * 7
         so.bh_transitions_pairs.restype = i
+        # telemetry_thin.hip (ops/gpu_thin.py): classify, mark
+        so.bh_thin_classify.argtypes = [p, p, i, i, i] + [p] * 7
+        so.bh_thin_classify.restype = i
+        so.bh_thin_mark.argtypes = [p, p, i, i, i] + [p] * 4
+        so.bh_thin_mark.restype = i
         _lib = so
     return _lib
 
