@@ -72,8 +72,7 @@ def policy_flags(policy) -> int:
 
 def coalesce_params(policy, slots: int, hash_mask: int = ALL_ONES) -> CoalesceParams:
     """``policy`` flattened for the kernels. Checks what they cannot: the 64-bit mask."""
-    if not 0 <= hash_mask <= ALL_ONES:
-        raise ValueError("hash_mask is 64-bit")
+    hash_mask = hip_lib.check_hash_mask(hash_mask)
     if slots < 2 or slots & (slots - 1) or slots > 1 << 32:
         raise ValueError("the group table's size is a power of two")
     return CoalesceParams(hash_mask, policy_flags(policy), slots - 1)
@@ -81,7 +80,7 @@ def coalesce_params(policy, slots: int, hash_mask: int = ALL_ONES) -> CoalescePa
 
 class Tables(NamedTuple):
     """The device tensors of one coalesce. ``select`` holds the extract's tensors over the same
-    ``keep_len``, ``cursor`` and ``overflow``, for ``gpu_extract.scan``, ``totals`` and ``gather``."""
+    ``keep_len``, for ``gpu_extract.scan``, ``totals`` and ``gather``."""
     n: int
     slots: int
     buf: object
@@ -94,53 +93,39 @@ class Tables(NamedTuple):
     keyed: object     # n uint8: 1 for a keyed frame
     cursor: object    # 1 int32: the length of overflow
     overflow: object  # n int32
-    select: gpu_extract.Tables
+    select: gpu_extract.ScanTables
 
 
 def allocate(buf_dev, offs_dev, n: int) -> Tables:
     """Tables for ``n`` frames next to ``buf_dev``, the group table zeroed. Checks the arguments on
     the host."""
     import torch
-    hip_lib.check_device_tensors(buf_dev, offs_dev, n)
-    if n < 1:
-        raise ValueError("the coalesce needs n >= 1")
-    if buf_dev.numel() >= 2 ** 31:
-        raise ValueError("stream too large for int32 offsets")
+    hip_lib.check_stream(buf_dev, offs_dev, n, "the coalesce")
     dev = buf_dev.device
     slots = gpu_fold.table_slots(n)
-    blocks = (n + gpu_extract.SCAN_BLOCK - 1) // gpu_extract.SCAN_BLOCK
 
     def empty(count, dtype):
         return torch.empty(count, dtype=dtype, device=dev)
-    keep_len, overflow = empty(n, torch.int32), empty(n, torch.int32)
-    cursor = torch.zeros(1, dtype=torch.int32, device=dev)
-    select = gpu_extract.Tables(n, buf_dev, offs_dev, None, None, keep_len, cursor, overflow,
-                                empty(blocks, torch.int64), empty(blocks + 1, torch.int64), empty(n, torch.int64),
-                                empty(n + 1, torch.int32), empty(n, torch.int32))
+    keep_len = empty(n, torch.int32)
     return Tables(n, slots, buf_dev, offs_dev, empty((n, 6), torch.int32),
                   torch.zeros(slots, dtype=torch.int64, device=dev), torch.zeros(slots, dtype=torch.int32, device=dev),
-                  empty(n, torch.int32), keep_len, empty(n, torch.uint8), cursor, overflow, select)
+                  empty(n, torch.int32), keep_len, empty(n, torch.uint8), torch.zeros(1, dtype=torch.int32, device=dev),
+                  empty(n, torch.int32), gpu_extract.scan_tables(keep_len, n, buf_dev, offs_dev))
 
 
 def launch(t: Tables, params: CoalesceParams, dialect: str = "protobufjs", stages: int = ALL_STAGES) -> None:
     """Classify, claim and/or mark (``stages``, a sum of ``STAGE_*``) over ``t`` on the current torch
     stream. ``t.offs`` must come from ``gpu_fold.index``: the kernels trust it. ``t.cursor``,
     ``t.claim`` and ``t.winner`` must be zero before classify and claim."""
-    import torch
     dialect_id = hip_lib.check_dialect(dialect)
     if not isinstance(stages, int) or not 1 <= stages <= ALL_STAGES:
         raise ValueError("stages is a sum of STAGE_CLASSIFY, STAGE_CLAIM and STAGE_MARK")
     if params.slot_mask + 1 != t.slots:
         raise ValueError("params were made for another table")
-    so = hip_lib.lib()
-    with torch.cuda.device(t.buf.device):
-        stream = torch.cuda.current_stream().cuda_stream
-        err = so.bh_coalesce_mark(t.buf.data_ptr(), t.offs.data_ptr(), t.n, dialect_id, ctypes.addressof(params),
-                                  t.rows.data_ptr(), t.cursor.data_ptr(), t.overflow.data_ptr(), t.claim.data_ptr(),
-                                  t.winner.data_ptr(), t.slot_of.data_ptr(), t.keep_len.data_ptr(),
-                                  t.keyed.data_ptr(), stages, stream)
-    if err:
-        raise RuntimeError(f"bh_coalesce_mark launch failed: hipError {err}")
+    hip_lib.call("bh_coalesce_mark", t.buf, t.buf.data_ptr(), t.offs.data_ptr(), t.n, dialect_id,
+                 ctypes.addressof(params), t.rows.data_ptr(), t.cursor.data_ptr(), t.overflow.data_ptr(),
+                 t.claim.data_ptr(), t.winner.data_ptr(), t.slot_of.data_ptr(), t.keep_len.data_ptr(),
+                 t.keyed.data_ptr(), stages)
 
 
 def device_groups(t: Tables, data, per_status: bool) -> dict:
@@ -174,17 +159,15 @@ def decide_on_host(t: Tables, data, offs: np.ndarray, policy, dialect: str = "pr
     count = int(t.cursor.item())
     if count == 0:
         return 0
-    frames = np.sort(t.overflow[:count].cpu().numpy())
+    frames, events = hip_lib.overflow_frames(t.overflow, count, data, offs)
     key = coalesce.key_of(policy, dialect)
-    view = memoryview(data)
     lengths = np.zeros(count, dtype=np.int32)
     keyed = np.zeros(count, dtype=np.uint8)
     last = {}  # key -> position in frames of its last host frame
-    for k, i in enumerate(frames.tolist()):
-        a, b = int(offs[i]), int(offs[i + 1])
-        answer = key(view[a + 4], bytes(view[a + 5:b]))
+    for k, (i, topic, body) in enumerate(events):
+        answer = key(topic, body)
         if answer is coalesce.KEEP:
-            lengths[k] = b - a
+            lengths[k] = int(offs[i + 1]) - int(offs[i])
         elif answer is not coalesce.DROP:
             keyed[k] = 1
             last[answer] = k  # frames ascend, so the last write is the last frame
@@ -233,20 +216,16 @@ def finish(data, offs: np.ndarray, indices: List[int], flags: np.ndarray, policy
 
 def coalesce(data, policy, device="cuda", dialect: str = "protobufjs", hash_mask: Optional[int] = None):
     """``(Coalesced, frames decided on the host)`` of a framed stream through the device."""
-    import torch
-
     from .. import coalesce as definition
     hip_lib.check_dialect(dialect)
-    if torch.device(device).type != "cuda":
-        raise ValueError(f"coalesce needs a GPU device, not {device!r}")
+    hip_lib.require_gpu(device, "coalesce")
     policy_flags(policy)
-    if hash_mask is not None and not 0 <= hash_mask <= ALL_ONES:
-        raise ValueError("hash_mask is 64-bit")
+    hash_mask = hip_lib.check_hash_mask(hash_mask)
     n, offs = gpu_fold.index(data)
     if n == 0:
         return definition.Coalesced(), 0
     hip_lib.lib()  # a missing library raises before anything is uploaded
-    params = coalesce_params(policy, gpu_fold.table_slots(n), ALL_ONES if hash_mask is None else hash_mask)
+    params = coalesce_params(policy, gpu_fold.table_slots(n), hash_mask)
     buf, offs_dev = gpu_fold.upload(data, offs, device)
     t = allocate(buf, offs_dev, n)
     launch(t, params, dialect)

@@ -60,11 +60,8 @@ def decode_batch(buf_dev, offs_dev, n: int, out_dev=None, dialect: str = "protob
         raise ValueError("out must be a contiguous (n, 8) int32 tensor")
     if n == 0:
         return out_dev
-    stream = torch.cuda.current_stream(buf_dev.device).cuda_stream
-    err = hip_lib.lib().bh_decode_telemetry(buf_dev.data_ptr(), offs_dev.data_ptr(), n, out_dev.data_ptr(), stream,
-                                            dialect_id)
-    if err:
-        raise RuntimeError(f"bh_decode_telemetry launch failed: hipError {err}")
+    hip_lib.call("bh_decode_telemetry", buf_dev, buf_dev.data_ptr(), offs_dev.data_ptr(), n, out_dev.data_ptr(),
+                 dialect_id)
     return out_dev
 
 

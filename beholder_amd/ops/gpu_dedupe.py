@@ -70,8 +70,7 @@ def dedupe_params(policy, slots: int, hash_mask: int = ALL_ONES, method: str = D
     """``policy`` flattened for the kernels. Checks what they cannot: the 64-bit mask."""
     _check_policy(policy)
     _check_method(method)
-    if not isinstance(hash_mask, int) or not 0 <= hash_mask <= ALL_ONES:
-        raise ValueError("hash_mask is 64-bit")
+    hash_mask = hip_lib.check_hash_mask(hash_mask)
     if slots < 2 or slots & (slots - 1) or slots > 1 << 32:
         raise ValueError("the table's size is a power of two")
     p = DedupeParams()
@@ -85,7 +84,7 @@ def dedupe_params(policy, slots: int, hash_mask: int = ALL_ONES, method: str = D
 
 class Tables(NamedTuple):
     """The device tensors of one dedupe. ``select`` holds the extract's tensors over the same
-    ``keep_len``, ``cursor`` and ``overflow``, for ``gpu_extract.scan``, ``totals`` and ``gather``."""
+    ``keep_len``, for ``gpu_extract.scan``, ``totals`` and ``gather``."""
     n: int
     slots: int
     buf: object
@@ -97,50 +96,36 @@ class Tables(NamedTuple):
     keep_len: object  # n int32: the frame's length where it is kept, else 0
     cursor: object    # 1 int32: the length of overflow
     overflow: object  # n int32
-    select: gpu_extract.Tables
+    select: gpu_extract.ScanTables
 
 
 def allocate(buf_dev, offs_dev, n: int) -> Tables:
     """Tables for ``n`` frames next to ``buf_dev``, the table zeroed. Checks the arguments on the host."""
     import torch
-    hip_lib.check_device_tensors(buf_dev, offs_dev, n)
-    if n < 1:
-        raise ValueError("the dedupe needs n >= 1")
-    if buf_dev.numel() >= 2 ** 31:
-        raise ValueError("stream too large for int32 offsets")
+    hip_lib.check_stream(buf_dev, offs_dev, n, "the dedupe")
     dev = buf_dev.device
     slots = gpu_fold.table_slots(n)
-    blocks = (n + gpu_extract.SCAN_BLOCK - 1) // gpu_extract.SCAN_BLOCK
 
     def empty(count, dtype):
         return torch.empty(count, dtype=dtype, device=dev)
-    keep_len, overflow = empty(n, torch.int32), empty(n, torch.int32)
-    cursor = torch.zeros(1, dtype=torch.int32, device=dev)
-    select = gpu_extract.Tables(n, buf_dev, offs_dev, None, None, keep_len, cursor, overflow,
-                                empty(blocks, torch.int64), empty(blocks + 1, torch.int64), empty(n, torch.int64),
-                                empty(n + 1, torch.int32), empty(n, torch.int32))
+    keep_len = empty(n, torch.int32)
     return Tables(n, slots, buf_dev, offs_dev, empty((n, 2), torch.int64),
                   torch.zeros(slots, dtype=torch.int64, device=dev), torch.zeros(slots, dtype=torch.int32, device=dev),
-                  empty(n, torch.int32), keep_len, cursor, overflow, select)
+                  empty(n, torch.int32), keep_len, torch.zeros(1, dtype=torch.int32, device=dev), empty(n, torch.int32),
+                  gpu_extract.scan_tables(keep_len, n, buf_dev, offs_dev))
 
 
 def launch(t: Tables, params: DedupeParams, stages: int = ALL_STAGES) -> None:
     """Hash, claim and/or mark (``stages``, a sum of ``STAGE_*``) over ``t`` on the current torch
     stream. ``t.offs`` must come from ``gpu_fold.index``: the kernels trust it. ``t.cursor``,
     ``t.claim`` and ``t.winner`` must be zero before hash and claim."""
-    import torch
     if not isinstance(stages, int) or not 1 <= stages <= ALL_STAGES:
         raise ValueError("stages is a sum of STAGE_HASH, STAGE_CLAIM and STAGE_MARK")
     if params.slot_mask + 1 != t.slots:
         raise ValueError("params were made for another table")
-    so = hip_lib.lib()
-    with torch.cuda.device(t.buf.device):
-        stream = torch.cuda.current_stream().cuda_stream
-        err = so.bh_dedupe_mark(t.buf.data_ptr(), t.offs.data_ptr(), t.n, ctypes.addressof(params),
-                                t.rows.data_ptr(), t.cursor.data_ptr(), t.overflow.data_ptr(), t.claim.data_ptr(),
-                                t.winner.data_ptr(), t.slot_of.data_ptr(), t.keep_len.data_ptr(), stages, stream)
-    if err:
-        raise RuntimeError(f"bh_dedupe_mark launch failed: hipError {err}")
+    hip_lib.call("bh_dedupe_mark", t.buf, t.buf.data_ptr(), t.offs.data_ptr(), t.n, ctypes.addressof(params),
+                 t.rows.data_ptr(), t.cursor.data_ptr(), t.overflow.data_ptr(), t.claim.data_ptr(),
+                 t.winner.data_ptr(), t.slot_of.data_ptr(), t.keep_len.data_ptr(), stages)
 
 
 def decide_on_host(t: Tables, data, offs: np.ndarray, policy) -> int:
@@ -151,11 +136,10 @@ def decide_on_host(t: Tables, data, offs: np.ndarray, policy) -> int:
     count = int(t.cursor.item())
     if count == 0:
         return 0
-    frames = np.sort(t.overflow[:count].cpu().numpy())
-    view = memoryview(data)
+    frames, events = hip_lib.overflow_frames(t.overflow, count, data, offs)
     winner = {}  # content -> position in frames of the one that is kept
-    for k, i in enumerate(frames.tolist()):
-        content = bytes(view[int(offs[i]) + 4:int(offs[i + 1])])
+    for k, (_, topic, body) in enumerate(events):
+        content = (topic, body)  # the topic byte and the body are the content
         if policy.keep == "last":
             winner[content] = k  # frames ascend, so the last write is the last frame
         else:
@@ -190,20 +174,16 @@ def collect(t: Tables, out, kept: int, data=None,
 
 def dedupe(data, policy, device="cuda", hash_mask: Optional[int] = None, method: str = DEFAULT_METHOD):
     """``(Deduped, frames decided on the host)`` of a framed stream through the device."""
-    import torch
-
     from .. import dedupe as definition
     _check_policy(policy)
     _check_method(method)
-    if torch.device(device).type != "cuda":
-        raise ValueError(f"dedupe needs a GPU device, not {device!r}")
-    if hash_mask is not None and (not isinstance(hash_mask, int) or not 0 <= hash_mask <= ALL_ONES):
-        raise ValueError("hash_mask is 64-bit")
+    hip_lib.require_gpu(device, "dedupe")
+    hash_mask = hip_lib.check_hash_mask(hash_mask)
     n, offs = gpu_fold.index(data)
     if n == 0:
         return definition.Deduped(keep=policy.keep, topics=policy.topics, hashes=np.zeros(0, dtype=np.uint64)), 0
     hip_lib.lib()  # a missing library raises before anything is uploaded
-    params = dedupe_params(policy, gpu_fold.table_slots(n), ALL_ONES if hash_mask is None else hash_mask, method)
+    params = dedupe_params(policy, gpu_fold.table_slots(n), hash_mask, method)
     buf, offs_dev = gpu_fold.upload(data, offs, device)
     t = allocate(buf, offs_dev, n)
     launch(t, params)

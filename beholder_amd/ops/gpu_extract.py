@@ -102,8 +102,7 @@ def build_media_table(ids: List[bytes], hash_mask: int = ALL_ONES) -> Tuple[np.n
 def select_params(selector, slots: int, hash_mask: int = ALL_ONES) -> SelectParams:
     """``selector`` flattened for the kernel. Checks what the kernel cannot: the 64-bit masks."""
     from .. import replay
-    if not 0 <= hash_mask <= ALL_ONES:
-        raise ValueError("hash_mask is 64-bit")
+    hash_mask = hip_lib.check_hash_mask(hash_mask)
     if slots < 2 or slots & (slots - 1):
         raise ValueError("the media table's size is a power of two")
     p = SelectParams()
@@ -120,6 +119,34 @@ def select_params(selector, slots: int, hash_mask: int = ALL_ONES) -> SelectPara
                | (F_UNKNOWN if selector.unknown_status else 0) | (F_INVERT if selector.invert else 0))
     p.slot_mask = slots - 1
     return p
+
+
+class ScanTables(NamedTuple):
+    """The device tensors that :func:`scan`, :func:`totals`, :func:`gather` and :func:`collect` read,
+    over any ``keep_len``: the other commands' way to the extract's prefix sum and copy. Their fields
+    are :class:`Tables`'s, so the four functions take either. A caller that fills ``pos``, ``out_offs``
+    and ``indices`` itself and only gathers (the shard) may leave ``totals`` and ``base`` ``None``."""
+    n: int
+    buf: object
+    offs: object
+    keep_len: object  # n int32: the frame's length where it is kept, else 0
+    totals: object    # blocks int64, scratch of the scan
+    base: object      # blocks + 1 int64; the last is kept << 32 | kept_bytes
+    pos: object       # n int64: output index << 32 | output byte offset
+    out_offs: object  # n + 1 int32
+    indices: object   # n int32
+
+
+def scan_tables(keep_len, count: int, buf, offs) -> ScanTables:
+    """Scratch and outputs of a scan over the ``count`` words of ``keep_len``, next to it."""
+    import torch
+    dev = keep_len.device
+    blocks = (count + SCAN_BLOCK - 1) // SCAN_BLOCK
+
+    def empty(size, dtype):
+        return torch.empty(size, dtype=dtype, device=dev)
+    return ScanTables(count, buf, offs, keep_len, empty(blocks, torch.int64), empty(blocks + 1, torch.int64),
+                      empty(count, torch.int64), empty(count + 1, torch.int32), empty(count, torch.int32))
 
 
 class Tables(NamedTuple):
@@ -143,29 +170,17 @@ def allocate(buf_dev, offs_dev, n: int, table: np.ndarray, blob: np.ndarray) -> 
     """Tables for ``n`` frames next to ``buf_dev``, the media table uploaded. Checks the arguments
     on the host."""
     import torch
-    hip_lib.check_device_tensors(buf_dev, offs_dev, n)
-    if n < 1:
-        raise ValueError("the extract needs n >= 1")
-    if buf_dev.numel() >= 2 ** 31:
-        raise ValueError("stream too large for int32 offsets")
+    hip_lib.check_stream(buf_dev, offs_dev, n, "the extract")
     if table.dtype != ENTRY or blob.dtype != np.uint8 or len(table) < 2 or len(table) & (len(table) - 1):
         raise ValueError("the media table is build_media_table's")
     dev = buf_dev.device
-    blocks = (n + SCAN_BLOCK - 1) // SCAN_BLOCK
-
-    def empty(count, dtype):
-        return torch.empty(count, dtype=dtype, device=dev)
+    keep_len = torch.empty(n, dtype=torch.int32, device=dev)
+    s = scan_tables(keep_len, n, buf_dev, offs_dev)
     return Tables(n, buf_dev, offs_dev,
                   torch.from_numpy(table.view(np.int64).reshape(-1, 2).copy()).to(dev),
                   torch.from_numpy(blob.copy()).to(dev),
-                  empty(n, torch.int32), torch.zeros(1, dtype=torch.int32, device=dev), empty(n, torch.int32),
-                  empty(blocks, torch.int64), empty(blocks + 1, torch.int64), empty(n, torch.int64),
-                  empty(n + 1, torch.int32), empty(n, torch.int32))
-
-
-def _stream(t: Tables):
-    import torch
-    return torch.cuda.device(t.buf.device), torch.cuda.current_stream(t.buf.device).cuda_stream
+                  keep_len, torch.zeros(1, dtype=torch.int32, device=dev),
+                  torch.empty(n, dtype=torch.int32, device=dev), s.totals, s.base, s.pos, s.out_offs, s.indices)
 
 
 def mark(t: Tables, params: SelectParams, dialect: str = "protobufjs") -> None:
@@ -174,14 +189,9 @@ def mark(t: Tables, params: SelectParams, dialect: str = "protobufjs") -> None:
     dialect_id = hip_lib.check_dialect(dialect)
     if params.slot_mask + 1 != t.table.shape[0]:
         raise ValueError("params were made for another table")
-    so = hip_lib.lib()
-    ctx, stream = _stream(t)
-    with ctx:
-        err = so.bh_select_mark(t.buf.data_ptr(), t.offs.data_ptr(), t.n, dialect_id,
-                                ctypes.addressof(params), t.table.data_ptr(), t.blob.data_ptr(),
-                                t.keep_len.data_ptr(), t.cursor.data_ptr(), t.overflow.data_ptr(), stream)
-    if err:
-        raise RuntimeError(f"bh_select_mark launch failed: hipError {err}")
+    hip_lib.call("bh_select_mark", t.buf, t.buf.data_ptr(), t.offs.data_ptr(), t.n, dialect_id,
+                 ctypes.addressof(params), t.table.data_ptr(), t.blob.data_ptr(), t.keep_len.data_ptr(),
+                 t.cursor.data_ptr(), t.overflow.data_ptr())
 
 
 def decide_on_host(t: Tables, data, offs: np.ndarray, selector, dialect: str = "protobufjs") -> int:
@@ -193,37 +203,31 @@ def decide_on_host(t: Tables, data, offs: np.ndarray, selector, dialect: str = "
     count = int(t.cursor.item())
     if count == 0:
         return 0
-    frames = np.sort(t.overflow[:count].cpu().numpy())
+    frames, events = hip_lib.overflow_frames(t.overflow, count, data, offs)
     keep = extract.predicate(selector, dialect)
-    view = memoryview(data)
     lengths = np.zeros(count, dtype=np.int32)
-    for k, i in enumerate(frames.tolist()):
-        a, b = int(offs[i]), int(offs[i + 1])
-        if keep(view[a + 4], bytes(view[a + 5:b])):
-            lengths[k] = b - a
+    for k, (i, topic, body) in enumerate(events):
+        if keep(topic, body):
+            lengths[k] = int(offs[i + 1]) - int(offs[i])
     dev = t.buf.device
     t.keep_len[torch.from_numpy(frames.astype(np.int64)).to(dev)] = torch.from_numpy(lengths).to(dev)
     return count
 
 
-def scan(t: Tables) -> None:
-    """The three scan launches over ``t.keep_len`` on the current torch stream."""
-    so = hip_lib.lib()
-    ctx, stream = _stream(t)
-    with ctx:
-        err = so.bh_select_scan(t.keep_len.data_ptr(), t.n, t.totals.data_ptr(), t.base.data_ptr(), t.pos.data_ptr(),
-                                t.out_offs.data_ptr(), t.indices.data_ptr(), stream)
-    if err:
-        raise RuntimeError(f"bh_select_scan launch failed: hipError {err}")
+def scan(t) -> None:
+    """The three scan launches over ``t.keep_len`` on the current torch stream. ``t`` is a
+    :class:`Tables` or a :class:`ScanTables`, here and in the functions below."""
+    hip_lib.call("bh_select_scan", t.keep_len, t.keep_len.data_ptr(), t.n, t.totals.data_ptr(), t.base.data_ptr(),
+                 t.pos.data_ptr(), t.out_offs.data_ptr(), t.indices.data_ptr())
 
 
-def totals(t: Tables) -> Tuple[int, int]:
+def totals(t) -> Tuple[int, int]:
     """``(kept, kept_bytes)`` after :func:`scan`: the one word the host reads to size the output."""
     word = int(t.base[-1].item())
     return word >> 32, word & 0xFFFFFFFF
 
 
-def gather(t: Tables, kept: int, kept_bytes: int, shape: str = DEFAULT_GATHER):
+def gather(t, kept: int, kept_bytes: int, shape: str = DEFAULT_GATHER):
     """The kept bytes in a new device buffer of exactly ``kept_bytes``. ``kept`` and ``kept_bytes``
     must be :func:`totals`'s: the kernels trust them."""
     import torch
@@ -234,18 +238,13 @@ def gather(t: Tables, kept: int, kept_bytes: int, shape: str = DEFAULT_GATHER):
     out = torch.empty(kept_bytes, dtype=torch.uint8, device=t.buf.device)
     if kept == 0:
         return out
-    so = hip_lib.lib()
-    ctx, stream = _stream(t)
-    with ctx:
-        err = so.bh_select_gather(t.buf.data_ptr(), t.offs.data_ptr(), t.n, t.keep_len.data_ptr(), t.pos.data_ptr(),
-                                  t.out_offs.data_ptr(), t.indices.data_ptr(), kept, kept_bytes, out.data_ptr(),
-                                  GATHER_SHAPES[shape], stream)
-    if err:
-        raise RuntimeError(f"bh_select_gather launch failed: hipError {err}")
+    hip_lib.call("bh_select_gather", t.buf, t.buf.data_ptr(), t.offs.data_ptr(), t.n, t.keep_len.data_ptr(),
+                 t.pos.data_ptr(), t.out_offs.data_ptr(), t.indices.data_ptr(), kept, kept_bytes, out.data_ptr(),
+                 GATHER_SHAPES[shape])
     return out
 
 
-def collect(t: Tables, out, kept: int) -> Tuple[bytes, List[int]]:
+def collect(t, out, kept: int) -> Tuple[bytes, List[int]]:
     """The output stream and the kept frames' input indices, on the host."""
     return out.cpu().numpy().tobytes(), t.indices[:kept].cpu().numpy().tolist()
 
@@ -253,16 +252,13 @@ def collect(t: Tables, out, kept: int) -> Tuple[bytes, List[int]]:
 def extract(data, selector, device="cuda", dialect: str = "protobufjs", hash_mask: Optional[int] = None,
             shape: str = DEFAULT_GATHER):
     """``(Extract, frames decided on the host)`` of a framed stream through the device."""
-    import torch
-
     from .. import extract as definition
     hip_lib.check_dialect(dialect)
-    if torch.device(device).type != "cuda":
-        raise ValueError(f"extract needs a GPU device, not {device!r}")
+    hip_lib.require_gpu(device, "extract")
     if shape not in GATHER_SHAPES:
         raise ValueError(f"unknown gather shape {shape!r} ({'|'.join(GATHER_SHAPES)})")
     ids = ascii_ids(selector.media)
-    params = select_params(selector, table_slots(len(ids)), ALL_ONES if hash_mask is None else hash_mask)
+    params = select_params(selector, table_slots(len(ids)), hash_mask)
     n, offs = gpu_fold.index(data)
     if n == 0:
         return definition.Extract(), 0

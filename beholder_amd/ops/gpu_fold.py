@@ -27,7 +27,7 @@ import numpy as np
 
 from . import hip_lib
 
-ALL_ONES = 0xFFFFFFFFFFFFFFFF
+ALL_ONES = hip_lib.ALL_ONES
 # counters[] of telemetry_fold.hip
 C_STATUS_ERR, C_PROGRESS_ERR, C_UNKNOWN_STATUS, C_OTHER_TOPIC, C_OVERFLOW, C_HIST, N_COUNTERS = 0, 1, 2, 3, 4, 8, 72
 
@@ -95,11 +95,7 @@ def upload(data, offs: np.ndarray, device="cuda") -> Tuple[object, object]:
 def allocate(buf_dev, offs_dev, n: int) -> Tables:
     """Zeroed tables for ``n`` frames next to ``buf_dev``. Checks the arguments on the host."""
     import torch
-    hip_lib.check_device_tensors(buf_dev, offs_dev, n)
-    if n < 1:
-        raise ValueError("the fold needs n >= 1")
-    if buf_dev.numel() >= 2 ** 31:
-        raise ValueError("stream too large for int32 offsets")
+    hip_lib.check_stream(buf_dev, offs_dev, n, "the fold")
     dev = buf_dev.device
     slots = table_slots(n)
     return Tables(n, slots, buf_dev, offs_dev,
@@ -114,18 +110,13 @@ def allocate(buf_dev, offs_dev, n: int) -> Tables:
 def launch(t: Tables, dialect: str = "protobufjs", mask: int = 0, hash_mask: int = ALL_ONES, passes: int = 3) -> None:
     """Pass A and/or pass B (``passes`` 1, 2 or 3) over ``t`` on the current torch stream. ``t.offs``
     must come from :func:`index`: the kernels trust it."""
-    import torch
     dialect_id = hip_lib.check_dialect(dialect)
-    if not 0 <= hash_mask <= ALL_ONES or not 0 <= mask <= ALL_ONES or passes not in (1, 2, 3):
-        raise ValueError("hash_mask and the status mask are 64-bit, passes is 1, 2 or 3")
-    so = hip_lib.lib()
-    with torch.cuda.device(t.buf.device):
-        stream = torch.cuda.current_stream().cuda_stream
-        err = so.bh_fold_telemetry(t.buf.data_ptr(), t.offs.data_ptr(), t.n, dialect_id, mask, hash_mask,
-                                   t.rows.data_ptr(), t.counters.data_ptr(), t.overflow.data_ptr(),
-                                   t.claim.data_ptr(), t.last.data_ptr(), t.counts.data_ptr(), t.slots, passes, stream)
-    if err:
-        raise RuntimeError(f"bh_fold_telemetry launch failed: hipError {err}")
+    hash_mask = hip_lib.check_hash_mask(hash_mask)
+    if not 0 <= mask <= ALL_ONES or passes not in (1, 2, 3):
+        raise ValueError("the status mask is 64-bit, passes is 1, 2 or 3")
+    hip_lib.call("bh_fold_telemetry", t.buf, t.buf.data_ptr(), t.offs.data_ptr(), t.n, dialect_id, mask, hash_mask,
+                 t.rows.data_ptr(), t.counters.data_ptr(), t.overflow.data_ptr(), t.claim.data_ptr(),
+                 t.last.data_ptr(), t.counts.data_ptr(), t.slots, passes)
 
 
 class Collected(NamedTuple):
@@ -135,7 +126,7 @@ class Collected(NamedTuple):
     id_len: np.ndarray
     counts: np.ndarray    # (groups, 3)
     last: np.ndarray      # groups, int64
-    overflow: np.ndarray  # sorted frame indices left to the host
+    overflow: object      # the frame indices left to the host, as the device listed them
 
 
 def collect(t: Tables) -> Collected:
@@ -143,8 +134,8 @@ def collect(t: Tables) -> Collected:
     used = t.claim.nonzero().squeeze(1)
     owner = t.claim[used] - 1
     ids = t.rows[owner, 2:4].cpu().numpy()
-    overflow = np.sort(t.overflow[:int(counters[C_OVERFLOW])].cpu().numpy())
-    return Collected(counters, ids[:, 0], ids[:, 1], t.counts[used].cpu().numpy(), t.last[used].cpu().numpy(), overflow)
+    return Collected(counters, ids[:, 0], ids[:, 1], t.counts[used].cpu().numpy(), t.last[used].cpu().numpy(),
+                     t.overflow[:int(counters[C_OVERFLOW])].cpu())
 
 
 def finish(data, offs: np.ndarray, n: int, c: Collected, dialect: str = "protobufjs"):
@@ -171,28 +162,23 @@ def finish(data, offs: np.ndarray, n: int, c: Collected, dialect: str = "protobu
             fold.last_status_index = ((last >> 32) & 0xFFFFFFFF) - 1
         media[str(view[off:off + length], "ascii")] = fold  # the device keeps ASCII ids only
     if len(c.overflow):
-        def events():
-            for i in c.overflow.tolist():
-                a, b = int(offs[i]), int(offs[i + 1])
-                yield i, view[a + 4], bytes(view[a + 5:b])
         # the host's frames may share media with the device's (upb), so they fold into the same summary
-        replay.fold_events(events(), dialect, into=s)
+        replay.fold_events(hip_lib.overflow_frames(c.overflow, len(c.overflow), data, offs)[1], dialect, into=s)
     return s
 
 
 def fold(data, device="cuda", dialect: str = "protobufjs", hash_mask: Optional[int] = None):
     """``(Summary, frames folded on the host)`` of a framed stream through the device."""
     from .. import replay
-    import torch
     hip_lib.check_dialect(dialect)
-    if torch.device(device).type != "cuda":
-        raise ValueError(f"fold needs a GPU device, not {device!r}")
+    hip_lib.require_gpu(device, "fold")
+    hash_mask = hip_lib.check_hash_mask(hash_mask)
     n, offs = index(data)
     if n == 0:
         return replay.Summary(), 0
     hip_lib.lib()  # a missing library raises before anything is uploaded
     buf, offs_dev = upload(data, offs, device)
     t = allocate(buf, offs_dev, n)
-    launch(t, dialect, known_mask(replay.status_names()), ALL_ONES if hash_mask is None else hash_mask)
+    launch(t, dialect, known_mask(replay.status_names()), hash_mask)
     c = collect(t)
     return finish(data, offs, n, c, dialect), len(c.overflow)

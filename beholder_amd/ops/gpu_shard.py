@@ -69,18 +69,14 @@ class Tables(NamedTuple):
     overflow: object  # n int32
     totals: object    # shards * blocks int64, shard-major: scratch of the partition
     base: object      # shards * blocks + 1 int64; [s * blocks] is frames << 32 | bytes before shard s
-    select: gpu_extract.Tables
+    select: gpu_extract.ScanTables
 
 
 def allocate(buf_dev, offs_dev, n: int, shards: int) -> Tables:
     """Tables for ``n`` frames and ``shards`` shards next to ``buf_dev``. Checks the arguments on
     the host."""
     import torch
-    hip_lib.check_device_tensors(buf_dev, offs_dev, n)
-    if n < 1:
-        raise ValueError("the shard needs n >= 1")
-    if buf_dev.numel() >= 2 ** 31:
-        raise ValueError("stream too large for int32 offsets")
+    hip_lib.check_stream(buf_dev, offs_dev, n, "the shard")
     if not isinstance(shards, int) or not 1 <= shards <= MAX_SHARDS:
         raise ValueError(f"shards must be in 1..{MAX_SHARDS}")
     blocks = (n + BLOCK_FRAMES - 1) // BLOCK_FRAMES
@@ -90,17 +86,12 @@ def allocate(buf_dev, offs_dev, n: int, shards: int) -> Tables:
 
     def empty(count, dtype):
         return torch.empty(count, dtype=dtype, device=dev)
-    cursor = torch.zeros(1, dtype=torch.int32, device=dev)
-    overflow = empty(n, torch.int32)
-    select = gpu_extract.Tables(n, buf_dev, offs_dev, None, None, empty(n, torch.int32), cursor, overflow, None, None,
-                                empty(n, torch.int64), empty(n + 1, torch.int32), empty(n, torch.int32))
-    return Tables(n, shards, blocks, buf_dev, offs_dev, empty(n, torch.int32), cursor, overflow,
+    # the partition fills pos, out_offs and indices itself: no scan, so none of its scratch
+    select = gpu_extract.ScanTables(n, buf_dev, offs_dev, empty(n, torch.int32), None, None, empty(n, torch.int64),
+                                    empty(n + 1, torch.int32), empty(n, torch.int32))
+    return Tables(n, shards, blocks, buf_dev, offs_dev, empty(n, torch.int32),
+                  torch.zeros(1, dtype=torch.int32, device=dev), empty(n, torch.int32),
                   empty(shards * blocks, torch.int64), empty(shards * blocks + 1, torch.int64), select)
-
-
-def _stream(t: Tables):
-    import torch
-    return torch.cuda.device(t.buf.device), torch.cuda.current_stream(t.buf.device).cuda_stream
 
 
 def route(t: Tables, params: ShardParams, dialect: str = "protobufjs") -> None:
@@ -109,13 +100,8 @@ def route(t: Tables, params: ShardParams, dialect: str = "protobufjs") -> None:
     dialect_id = hip_lib.check_dialect(dialect)
     if params.shards != t.shards:
         raise ValueError("params were made for another shard count")
-    so = hip_lib.lib()
-    ctx, stream = _stream(t)
-    with ctx:
-        err = so.bh_shard_route(t.buf.data_ptr(), t.offs.data_ptr(), t.n, dialect_id, ctypes.addressof(params),
-                                t.shard_of.data_ptr(), t.cursor.data_ptr(), t.overflow.data_ptr(), stream)
-    if err:
-        raise RuntimeError(f"bh_shard_route launch failed: hipError {err}")
+    hip_lib.call("bh_shard_route", t.buf, t.buf.data_ptr(), t.offs.data_ptr(), t.n, dialect_id,
+                 ctypes.addressof(params), t.shard_of.data_ptr(), t.cursor.data_ptr(), t.overflow.data_ptr())
 
 
 def decide_on_host(t: Tables, data, offs: np.ndarray, policy, dialect: str = "protobufjs") -> int:
@@ -127,13 +113,11 @@ def decide_on_host(t: Tables, data, offs: np.ndarray, policy, dialect: str = "pr
     count = int(t.cursor.item())
     if count == 0:
         return 0
-    frames = np.sort(t.overflow[:count].cpu().numpy())
+    frames, events = hip_lib.overflow_frames(t.overflow, count, data, offs)
     where = shard.route_of(policy, dialect)
-    view = memoryview(data)
     shards = np.full(count, -1, dtype=np.int32)
-    for k, i in enumerate(frames.tolist()):
-        a, b = int(offs[i]), int(offs[i + 1])
-        s = where(view[a + 4], bytes(view[a + 5:b]))
+    for k, (_, topic, body) in enumerate(events):
+        s = where(topic, body)
         if s is not shard.DROP:
             shards[k] = s
     dev = t.buf.device
@@ -148,15 +132,10 @@ def partition(t: Tables, method: str = DEFAULT_METHOD, stages: int = ALL_STAGES)
         raise ValueError(f"unknown method {method!r} ({'|'.join(METHODS)})")
     if not isinstance(stages, int) or not 1 <= stages <= ALL_STAGES:
         raise ValueError("stages is a sum of STAGE_COUNT, STAGE_TOTALS and STAGE_APPLY")
-    so = hip_lib.lib()
     s = t.select
-    ctx, stream = _stream(t)
-    with ctx:
-        err = so.bh_shard_partition(t.shard_of.data_ptr(), t.offs.data_ptr(), t.n, t.shards, t.totals.data_ptr(),
-                                    t.base.data_ptr(), s.pos.data_ptr(), s.keep_len.data_ptr(), s.out_offs.data_ptr(),
-                                    s.indices.data_ptr(), METHODS[method], stages, stream)
-    if err:
-        raise RuntimeError(f"bh_shard_partition launch failed: hipError {err}")
+    hip_lib.call("bh_shard_partition", t.buf, t.shard_of.data_ptr(), t.offs.data_ptr(), t.n, t.shards,
+                 t.totals.data_ptr(), t.base.data_ptr(), s.pos.data_ptr(), s.keep_len.data_ptr(),
+                 s.out_offs.data_ptr(), s.indices.data_ptr(), METHODS[method], stages)
 
 
 def boundaries(t: Tables) -> Tuple[np.ndarray, np.ndarray]:
@@ -177,12 +156,9 @@ def collect(t: Tables, out, first: np.ndarray, starts: np.ndarray) -> Tuple[List
 def shard(data, policy, device="cuda", dialect: str = "protobufjs", shape: str = gpu_extract.DEFAULT_GATHER,
           method: str = DEFAULT_METHOD):
     """``(Sharded, frames decided on the host)`` of a framed stream through the device."""
-    import torch
-
     from .. import shard as definition
     hip_lib.check_dialect(dialect)
-    if torch.device(device).type != "cuda":
-        raise ValueError(f"shard needs a GPU device, not {device!r}")
+    hip_lib.require_gpu(device, "shard")
     params = shard_params(policy)
     if shape not in gpu_extract.GATHER_SHAPES:
         raise ValueError(f"unknown gather shape {shape!r} ({'|'.join(gpu_extract.GATHER_SHAPES)})")

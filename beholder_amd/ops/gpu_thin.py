@@ -37,7 +37,6 @@ from typing import NamedTuple, Optional, Tuple
 import numpy as np
 
 from . import gpu_extract, gpu_fold, gpu_transitions, hip_lib
-from .gpu_fold import ALL_ONES
 
 C_PROGRESS_ERR, C_OVERFLOW, C_DROPPED, N_COUNTERS = 0, 1, 2, 3  # counters[] of telemetry_thin.hip
 STEP_MAX = 2 ** 31 - 1
@@ -51,7 +50,7 @@ class Tables(NamedTuple):
     t: gpu_transitions.Tables
     marks: object     # n int64: the mark word of a progress event, else 0
     keep_len: object  # n int32: the frame's length where it is kept, else 0
-    select: gpu_extract.Tables
+    select: gpu_extract.ScanTables
 
 
 def _check_policy(policy) -> None:
@@ -71,7 +70,7 @@ def allocate(buf_dev, offs_dev, n: int) -> Tables:
     t = t._replace(counters=torch.zeros(N_COUNTERS, dtype=torch.int32, device=dev))
     keep_len = torch.empty(n, dtype=torch.int32, device=dev)
     return Tables(t, torch.empty(n, dtype=torch.int64, device=dev), keep_len,
-                  gpu_transitions._scan_tables(keep_len, n, buf_dev, offs_dev))
+                  gpu_extract.scan_tables(keep_len, n, buf_dev, offs_dev))
 
 
 def classify(tb: Tables, policy, dialect: str = "protobufjs") -> None:
@@ -79,15 +78,10 @@ def classify(tb: Tables, policy, dialect: str = "protobufjs") -> None:
     ``gpu_fold.index``: the kernel trusts it. ``tb.t.counters`` must be zero."""
     _check_policy(policy)
     dialect_id = hip_lib.check_dialect(dialect)
-    so = hip_lib.lib()
     t = tb.t
-    ctx, stream = gpu_transitions._stream(t.buf)
-    with ctx:
-        err = so.bh_thin_classify(t.buf.data_ptr(), t.offs.data_ptr(), t.n, dialect_id, policy.step, t.rows.data_ptr(),
-                                  t.is_event.data_ptr(), tb.marks.data_ptr(), tb.keep_len.data_ptr(),
-                                  t.counters.data_ptr(), t.overflow.data_ptr(), stream)
-    if err:
-        raise RuntimeError(f"bh_thin_classify launch failed: hipError {err}")
+    hip_lib.call("bh_thin_classify", t.buf, t.buf.data_ptr(), t.offs.data_ptr(), t.n, dialect_id, policy.step,
+                 t.rows.data_ptr(), t.is_event.data_ptr(), tb.marks.data_ptr(), tb.keep_len.data_ptr(),
+                 t.counters.data_ptr(), t.overflow.data_ptr())
 
 
 def mark(tb: Tables, s: gpu_transitions.Sorted, policy) -> None:
@@ -95,13 +89,8 @@ def mark(tb: Tables, s: gpu_transitions.Sorted, policy) -> None:
     _check_policy(policy)
     if not 1 <= s.events <= tb.t.n:
         raise ValueError("the events are the scan's total, and there is at least one")
-    so = hip_lib.lib()
-    ctx, stream = gpu_transitions._stream(s.keys)
-    with ctx:
-        err = so.bh_thin_mark(s.keys.data_ptr(), s.vals.data_ptr(), s.events, tb.t.n, int(policy.keep == "first"),
-                              tb.marks.data_ptr(), tb.keep_len.data_ptr(), tb.t.counters.data_ptr(), stream)
-    if err:
-        raise RuntimeError(f"bh_thin_mark launch failed: hipError {err}")
+    hip_lib.call("bh_thin_mark", s.keys, s.keys.data_ptr(), s.vals.data_ptr(), s.events, tb.t.n,
+                 int(policy.keep == "first"), tb.marks.data_ptr(), tb.keep_len.data_ptr(), tb.t.counters.data_ptr())
 
 
 def _word(m: tuple) -> int:
@@ -123,13 +112,11 @@ def decide_on_host(tb: Tables, s: Optional[gpu_transitions.Sorted], data, offs: 
     count = int(t.counters.cpu().numpy()[C_OVERFLOW])
     if count == 0:
         return 0, 0
-    frames = np.sort(t.overflow[:count].cpu().numpy()).tolist()
     mark_of = thin.mark_of(policy, dialect)
     view = memoryview(data)
     per_media = {}  # id -> its (frame, mark word) pairs from the host's frames, in stream order
-    for i in frames:
-        a, b = int(offs[i]), int(offs[i + 1])
-        m = mark_of(view[a + 4], bytes(view[a + 5:b]))
+    for i, topic, body in hip_lib.overflow_frames(t.overflow, count, data, offs)[1]:
+        m = mark_of(topic, body)
         if m is not None:
             per_media.setdefault(m[0], []).append((i, _word(m)))
     host_events = sum(map(len, per_media.values()))
@@ -163,16 +150,11 @@ def decide_on_host(tb: Tables, s: Optional[gpu_transitions.Sorted], data, offs: 
 
 def thin(data, policy, device="cuda", dialect: str = "protobufjs", hash_mask: Optional[int] = None):
     """``(Thinned, frames decoded on the host)`` of a framed stream through the device."""
-    import torch
-
     from .. import thin as definition
     _check_policy(policy)
     hip_lib.check_dialect(dialect)
-    if torch.device(device).type != "cuda":
-        raise ValueError(f"thin needs a GPU device, not {device!r}")
-    hash_mask = ALL_ONES if hash_mask is None else hash_mask
-    if not isinstance(hash_mask, int) or isinstance(hash_mask, bool) or not 0 <= hash_mask <= ALL_ONES:
-        raise ValueError("hash_mask is 64-bit")
+    hip_lib.require_gpu(device, "thin")
+    hash_mask = hip_lib.check_hash_mask(hash_mask)
     n, offs = gpu_fold.index(data)  # raises for a stream of 2^31 bytes or more
     if n == 0:
         return definition.Thinned(step=policy.step, keep=policy.keep, dialect=dialect), 0

@@ -65,8 +65,8 @@ class Tables(NamedTuple):
     claim: object      # slots int64: 0 or 1 + the frame that claimed the slot
     slot_used: object  # slots int32
     slot_of: object    # n int32
-    slot_scan: gpu_extract.Tables
-    event_scan: gpu_extract.Tables
+    slot_scan: gpu_extract.ScanTables
+    event_scan: gpu_extract.ScanTables
 
 
 class Sorted(NamedTuple):
@@ -83,27 +83,11 @@ class Sorted(NamedTuple):
     changes: object    # groups int32
 
 
-def _scan_tables(keep_len, count: int, buf, offs) -> gpu_extract.Tables:
-    import torch
-    dev = keep_len.device
-    blocks = (count + gpu_extract.SCAN_BLOCK - 1) // gpu_extract.SCAN_BLOCK
-
-    def empty(size, dtype):
-        return torch.empty(size, dtype=dtype, device=dev)
-    return gpu_extract.Tables(count, buf, offs, None, None, keep_len, None, None, empty(blocks, torch.int64),
-                              empty(blocks + 1, torch.int64), empty(count, torch.int64),
-                              empty(count + 1, torch.int32), empty(count, torch.int32))
-
-
 def allocate(buf_dev, offs_dev, n: int) -> Tables:
     """Tables for ``n`` frames next to ``buf_dev``, zeroed where the kernels need it. Checks the
     arguments on the host."""
     import torch
-    hip_lib.check_device_tensors(buf_dev, offs_dev, n)
-    if n < 1:
-        raise ValueError("transitions needs n >= 1")
-    if buf_dev.numel() >= 2 ** 31:
-        raise ValueError("stream too large for int32 offsets")
+    hip_lib.check_stream(buf_dev, offs_dev, n, "transitions")
     slots = gpu_fold.table_slots(n)
     if slots > MAX_SLOTS:
         raise ValueError("the media table is too large for int32 indexing: cut the stream into chunks")
@@ -116,38 +100,23 @@ def allocate(buf_dev, offs_dev, n: int) -> Tables:
                   torch.empty(n, dtype=torch.int32, device=dev),
                   torch.zeros(slots, dtype=torch.int64, device=dev), slot_used,
                   torch.empty(n, dtype=torch.int32, device=dev),
-                  _scan_tables(slot_used, slots, buf_dev, offs_dev), _scan_tables(is_event, n, buf_dev, offs_dev))
-
-
-def _stream(buf):
-    import torch
-    return torch.cuda.device(buf.device), torch.cuda.current_stream(buf.device).cuda_stream
+                  gpu_extract.scan_tables(slot_used, slots, buf_dev, offs_dev),
+                  gpu_extract.scan_tables(is_event, n, buf_dev, offs_dev))
 
 
 def classify(t: Tables, dialect: str = "protobufjs") -> None:
     """The classify launch over ``t`` on the current torch stream. ``t.offs`` must come from
     ``gpu_fold.index``: the kernel trusts it. ``t.counters`` must be zero."""
     dialect_id = hip_lib.check_dialect(dialect)
-    so = hip_lib.lib()
-    ctx, stream = _stream(t.buf)
-    with ctx:
-        err = so.bh_transitions_classify(t.buf.data_ptr(), t.offs.data_ptr(), t.n, dialect_id, t.rows.data_ptr(),
-                                         t.is_event.data_ptr(), t.counters.data_ptr(), t.overflow.data_ptr(), stream)
-    if err:
-        raise RuntimeError(f"bh_transitions_classify launch failed: hipError {err}")
+    hip_lib.call("bh_transitions_classify", t.buf, t.buf.data_ptr(), t.offs.data_ptr(), t.n, dialect_id,
+                 t.rows.data_ptr(), t.is_event.data_ptr(), t.counters.data_ptr(), t.overflow.data_ptr())
 
 
 def claim(t: Tables, hash_mask: int = ALL_ONES) -> None:
     """The claim launch over the rows of :func:`classify`. ``t.claim`` and ``t.slot_used`` must be zero."""
-    if not isinstance(hash_mask, int) or not 0 <= hash_mask <= ALL_ONES:
-        raise ValueError("hash_mask is 64-bit")
-    so = hip_lib.lib()
-    ctx, stream = _stream(t.buf)
-    with ctx:
-        err = so.bh_transitions_claim(t.buf.data_ptr(), t.rows.data_ptr(), t.n, hash_mask, t.claim.data_ptr(),
-                                      t.slot_used.data_ptr(), t.slot_of.data_ptr(), t.slots, stream)
-    if err:
-        raise RuntimeError(f"bh_transitions_claim launch failed: hipError {err}")
+    hash_mask = hip_lib.check_hash_mask(hash_mask)
+    hip_lib.call("bh_transitions_claim", t.buf, t.buf.data_ptr(), t.rows.data_ptr(), t.n, hash_mask,
+                 t.claim.data_ptr(), t.slot_used.data_ptr(), t.slot_of.data_ptr(), t.slots)
 
 
 def rank(t: Tables) -> None:
@@ -178,13 +147,8 @@ def compact(t: Tables, groups: int, events: int) -> Sorted:
                torch.zeros(CLASSES * CLASSES, dtype=torch.int32, device=dev), empty(groups, torch.int64),
                empty(groups, torch.int64), empty(groups, torch.int32), empty(groups, torch.int32),
                torch.zeros(groups, dtype=torch.int32, device=dev))
-    so = hip_lib.lib()
-    ctx, stream = _stream(t.buf)
-    with ctx:
-        err = so.bh_transitions_compact(t.rows.data_ptr(), t.event_scan.indices.data_ptr(), t.slot_of.data_ptr(),
-                                        t.slot_scan.pos.data_ptr(), events, s.keys.data_ptr(), s.vals.data_ptr(), stream)
-    if err:
-        raise RuntimeError(f"bh_transitions_compact launch failed: hipError {err}")
+    hip_lib.call("bh_transitions_compact", t.buf, t.rows.data_ptr(), t.event_scan.indices.data_ptr(),
+                 t.slot_of.data_ptr(), t.slot_scan.pos.data_ptr(), events, s.keys.data_ptr(), s.vals.data_ptr())
     return s
 
 
@@ -204,13 +168,8 @@ def sort_pass(keys, vals, events: int, shift: int, totals, base, keys_out, vals_
         raise ValueError("shift is 0, 8, 16 or 24")
     if not isinstance(stages, int) or not 1 <= stages <= ALL_STAGES:
         raise ValueError("stages is a sum of STAGE_COUNT, STAGE_TOTALS and STAGE_APPLY")
-    so = hip_lib.lib()
-    ctx, stream = _stream(keys)
-    with ctx:
-        err = so.bh_transitions_sort_pass(keys.data_ptr(), vals.data_ptr(), events, shift, totals.data_ptr(),
-                                          base.data_ptr(), keys_out.data_ptr(), vals_out.data_ptr(), stages, stream)
-    if err:
-        raise RuntimeError(f"bh_transitions_sort_pass launch failed: hipError {err}")
+    hip_lib.call("bh_transitions_sort_pass", keys, keys.data_ptr(), vals.data_ptr(), events, shift, totals.data_ptr(),
+                 base.data_ptr(), keys_out.data_ptr(), vals_out.data_ptr(), stages)
 
 
 def sort(s: Sorted, passes: Optional[int] = None) -> Sorted:
@@ -234,20 +193,15 @@ def pairs(s: Sorted, mask: int) -> None:
     ``s.matrix`` and ``s.changes`` must be zero."""
     if not isinstance(mask, int) or not 0 <= mask <= ALL_ONES:
         raise ValueError("the status mask is 64-bit")
-    so = hip_lib.lib()
-    ctx, stream = _stream(s.keys)
-    with ctx:
-        err = so.bh_transitions_pairs(s.keys.data_ptr(), s.vals.data_ptr(), s.events, s.groups, mask,
-                                      s.matrix.data_ptr(), s.first.data_ptr(), s.last.data_ptr(),
-                                      s.run_start.data_ptr(), s.run_end.data_ptr(), s.changes.data_ptr(), stream)
-    if err:
-        raise RuntimeError(f"bh_transitions_pairs launch failed: hipError {err}")
+    hip_lib.call("bh_transitions_pairs", s.keys, s.keys.data_ptr(), s.vals.data_ptr(), s.events, s.groups, mask,
+                 s.matrix.data_ptr(), s.first.data_ptr(), s.last.data_ptr(), s.run_start.data_ptr(),
+                 s.run_end.data_ptr(), s.changes.data_ptr())
 
 
 class Collected(NamedTuple):
     """What crosses back to the host: O(classes^2 + media + overflow)."""
     counters: np.ndarray   # N_COUNTERS
-    overflow: np.ndarray   # sorted frame indices left to the host
+    overflow: object       # the frame indices left to the host, as the device listed them
     matrix: np.ndarray     # (CLASSES, CLASSES)
     id_off: np.ndarray     # per media number
     id_len: np.ndarray
@@ -261,7 +215,7 @@ class Collected(NamedTuple):
 def collect(t: Tables, s: Optional[Sorted]) -> Collected:
     """``s`` is None where the stream has no status event that the device decided."""
     counters = t.counters.cpu().numpy()
-    overflow = np.sort(t.overflow[:int(counters[C_OVERFLOW])].cpu().numpy())
+    overflow = t.overflow[:int(counters[C_OVERFLOW])].cpu()
     if s is None:
         none = np.zeros(0, dtype=np.int64)
         return Collected(counters, overflow, np.zeros((CLASSES, CLASSES), dtype=np.int64), none, none, none, none, none,
@@ -303,11 +257,8 @@ def finish(data, offs: np.ndarray, n: int, c: Collected, s: Optional[Sorted], di
         t.status_events += end - start
         number[mid] = k
     if len(c.overflow):
-        def events():
-            for i in c.overflow.tolist():
-                a, b = int(offs[i]), int(offs[i + 1])
-                yield i, view[a + 4], bytes(view[a + 5:b])
-        per_media, errors = definition.status_events_of(events(), dialect)
+        events = hip_lib.overflow_frames(c.overflow, len(c.overflow), data, offs)[1]
+        per_media, errors = definition.status_events_of(events, dialect)
         t.status_decode_errors += errors
         for mid, mine in per_media.items():
             k = number.get(mid)
@@ -324,15 +275,10 @@ def finish(data, offs: np.ndarray, n: int, c: Collected, s: Optional[Sorted], di
 
 def transitions(data, device="cuda", dialect: str = "protobufjs", hash_mask: Optional[int] = None):
     """``(Transitions, frames decoded on the host)`` of a framed stream through the device."""
-    import torch
-
     from .. import replay, transitions as definition
     hip_lib.check_dialect(dialect)
-    if torch.device(device).type != "cuda":
-        raise ValueError(f"transitions needs a GPU device, not {device!r}")
-    hash_mask = ALL_ONES if hash_mask is None else hash_mask
-    if not isinstance(hash_mask, int) or not 0 <= hash_mask <= ALL_ONES:
-        raise ValueError("hash_mask is 64-bit")
+    hip_lib.require_gpu(device, "transitions")
+    hash_mask = hip_lib.check_hash_mask(hash_mask)
     n, offs = gpu_fold.index(data)
     if n == 0:
         return definition.Transitions(), 0

@@ -14,11 +14,9 @@
 //    drop, keep, keyed, or left to the host. Writes one 24-byte row
 //      {hash, id_off, id_len, status, kind | topic}
 //    Frames left to the host go to an overflow list through an atomic cursor.
-//  claim, coalesce_claim, one lane per keyed frame. The fold's pass B: open addressing over `slots`
-//    (a power of two, >= 2n) entries, the home slot is hash & hash_mask & (slots - 1), a lane claims
-//    an empty slot with a 64-bit compare-and-swap of m + 1, and where the slot is taken it compares
-//    topic, status, length, hash and then the bytes of the claimant's id, so nothing depends on the
-//    hash being free of collisions. It moves to the next slot on a mismatch, wrapping at the end.
+//  claim, coalesce_claim, one lane per keyed frame finds its key's slot in the group table
+//    (media_table.hpp claim_slot over `slots` entries, a power of two, >= 2n): keys are the same
+//    where topic, status, length, hash and then the id's bytes are.
 //    Then an atomic max of m + 1 on the slot's winner word: the winner is the key's last frame by
 //    index, not by arrival, so every result is the same from run to run. The lane writes its slot
 //    to slot_of[m].
@@ -27,11 +25,8 @@
 //    frame. Host frames get 0 here; the host decides them and scatters their lengths into keep_len
 //    before the scan.
 //
-// Visibility is the fold's rule: within a launch workgroups meet only in atomics (the cursor, the
-// claims, the winners). Every plain load reads what an earlier launch or the host wrote: claim reads
-// the rows of classify, mark reads slot_of and the winners of claim. No kernel waits for another
-// workgroup. That is why classify and claim are two kernels: a claimant's row must be visible to
-// every lane that meets its claim.
+// Visibility is media_table.hpp's rule: claim reads the rows of classify, mark reads slot_of and the
+// winners of claim.
 #include "telemetry_coalesce.hpp"
 
 namespace {
@@ -87,22 +82,12 @@ __global__ __launch_bounds__(BLOCK) void coalesce_claim(const uint8_t* __restric
   const CoalesceRow row = rows[m];
   if ((row.flags & R_KIND) != CL_KEYED) return;
   const unsigned long long me = static_cast<unsigned long long>(m) + 1ull;
-  uint32_t slot = static_cast<uint32_t>(row.hash & hash_mask) & slot_mask;
-  for (;;) {  // ends: the keys are at most n, the slots at least 2n
-    // a claim is written once and never changes, so a non-zero value read here is final
-    unsigned long long owner = __hip_atomic_load(&claim[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (owner == 0) owner = atomicCAS(&claim[slot], 0ull, me);
-    if (owner == 0) break;  // claimed
-    const CoalesceRow o = rows[owner - 1];  // a keyed row: only keyed lanes claim
-    if (o.flags == row.flags && o.status == row.status && o.id_len == row.id_len && o.hash == row.hash) {
-      const uint8_t* __restrict__ a = buf + o.id_off;
-      const uint8_t* __restrict__ b = buf + row.id_off;
-      int k = 0;
-      while (k < row.id_len && a[k] == b[k]) ++k;
-      if (k == row.id_len) break;  // the same key
-    }
-    slot = (slot + 1) & slot_mask;
-  }
+  const auto same_key = [&](unsigned long long owner) {
+    const CoalesceRow o = rows[owner];  // a keyed row: only keyed lanes claim
+    return o.flags == row.flags && o.status == row.status && o.id_len == row.id_len && o.hash == row.hash &&
+           bytes_equal(buf + o.id_off, buf + row.id_off, row.id_len);
+  };
+  const uint32_t slot = claim_slot(claim, slot_mask, home_slot(row.hash, hash_mask, slot_mask), me, same_key).slot;
   atomicMax(&winner[slot], static_cast<uint32_t>(me));  // n < 2^31
   slot_of[m] = static_cast<int32_t>(slot);
 }

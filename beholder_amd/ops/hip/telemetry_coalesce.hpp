@@ -13,7 +13,7 @@
 //
 // The policy (coalesce.Policy) arrives flattened into CoalesceParams::flags.
 #pragma once
-#include "telemetry_readers.hpp"
+#include "media_table.hpp"
 
 namespace bh {
 
@@ -43,33 +43,15 @@ struct CoalesceKey {
   uint32_t topic;  // 1 or 2
 };
 
-// The fold's hash of the id bytes (FNV-1a, then murmur3's 64-bit finaliser), then the topic and the
-// status mixed in: ops/gpu_coalesce.py key_hash is the same. It only orders the probe. `high` is
-// non-zero where an id byte is >= 0x80.
+// The fold's hash of the id bytes (media_table.hpp hash64_bytes), then the topic and the status
+// mixed in: ops/gpu_coalesce.py key_hash is the same. It only orders the probe. `high` is non-zero
+// where an id byte is >= 0x80.
 BH_FN uint64_t key_hash(const uint8_t* __restrict__ p, int n, uint32_t topic, int32_t status, uint32_t& high) {
-  uint64_t h = 0xcbf29ce484222325ull;
-  uint32_t any = 0;
-  for (int k = 0; k < n; ++k) {
-    const uint32_t b = p[k];
-    any |= b;
-    h = (h ^ b) * 0x100000001b3ull;
-  }
-  h ^= h >> 33;
-  h *= 0xff51afd7ed558ccdull;
-  h ^= h >> 33;
-  h *= 0xc4ceb9fe1a85ec53ull;
-  h ^= h >> 33;
+  uint64_t h = hash64_bytes(p, n, high);
   h ^= (static_cast<uint64_t>(topic) << 32) | static_cast<uint32_t>(status);
   h *= 0xff51afd7ed558ccdull;
   h ^= h >> 33;
-  high = any & 0x80u;
   return h;
-}
-
-BH_FN bool coalesce_high_byte(const uint8_t* __restrict__ p, int n) {
-  uint32_t any = 0;
-  for (int k = 0; k < n; ++k) any |= p[k];
-  return (any & 0x80u) != 0;
 }
 
 template <int DIALECT>
@@ -92,7 +74,7 @@ BH_FN int classify(const uint8_t* __restrict__ buf, const int head, const int en
   uint32_t high;
   key.hash = key_hash(buf + r.id_off, r.id_len, topic, status, high);
   if (high) return CL_HOST;
-  if (DIALECT == DIALECT_UPB && !is_status && coalesce_high_byte(buf + r.host_off, r.host_len)) return CL_HOST;
+  if (DIALECT == DIALECT_UPB && !is_status && has_high_byte(buf + r.host_off, r.host_len)) return CL_HOST;
   key.id_off = r.id_off;
   key.id_len = r.id_len;
   key.status = status;

@@ -43,7 +43,7 @@ __global__ __launch_bounds__(256) void decode_telemetry(const uint8_t* __restric
 // caller's device; `stream` is the torch stream (hipStream_t); `dialect` 0 = upb, 1 = protobufjs.
 // Returns a hipError_t (hipErrorInvalidValue for an unknown dialect).
 extern "C" __attribute__((visibility("default"))) int bh_decode_telemetry(const void* buf, const void* offs, int n,
-                                                                         void* out, void* stream, int dialect) {
+                                                                         void* out, int dialect, void* stream) {
   if (n <= 0) return 0;
   if (dialect != DIALECT_UPB && dialect != DIALECT_PROTOBUFJS) return static_cast<int>(hipErrorInvalidValue);
   const int block = 256;

@@ -15,12 +15,10 @@
 //    DEDUPE_DEVICE_MAX goes to an overflow list through an atomic cursor: the host decides those.
 //    Every other frame gets its 64-bit content hash. Writes one 16-byte row {hash, off, len}:
 //    len is the content's length, 0 for KEEP and -1 for a host frame.
-//  claim, dedupe_claim, one lane per frame that takes part. The coalesce's claim with a longer key:
-//    open addressing over `slots` (a power of two, >= 2n) entries, the home slot is
-//    hash & hash_mask & (slots - 1), a lane claims an empty slot with a 64-bit compare-and-swap of
-//    m + 1, and where the slot is taken it compares length, then hash, then the content's bytes, so
-//    nothing depends on the hash (hash_mask = 0 stays exact). It moves to the next slot on a
-//    mismatch, wrapping at the end. Then one atomic max on the slot's winner word, of m + 1 under
+//  claim, dedupe_claim, one lane per frame that takes part finds its content's slot in the table
+//    (media_table.hpp claim_slot over `slots` entries, a power of two, >= 2n): contents are the same
+//    where length, then hash, then the bytes are, so nothing depends on the hash (hash_mask = 0
+//    stays exact). Then one atomic max on the slot's winner word, of m + 1 under
 //    keep=last and of n - m under keep=first: the winner is the content's last or first frame by
 //    index, not by arrival, so every result is the same from run to run, and the table starts from
 //    zeros either way. The lane writes its slot to slot_of[m].
@@ -31,14 +29,10 @@
 // A host frame is longer than the cap and a device frame is not, so the two never share a content:
 // unlike the coalesce there is no step that resolves host against device.
 //
-// Every loop over bytes is bounded by DEDUPE_DEVICE_MAX; the probe loop ends because the contents
-// are at most n and the slots at least 2n.
+// Every loop over bytes is bounded by DEDUPE_DEVICE_MAX, the walk by the table's size.
 //
-// Visibility is the fold's rule: within a launch workgroups meet only in atomics (the cursor, the
-// claims, the winners). Every plain load reads what an earlier launch or the host wrote: claim reads
-// the rows of hash and the stream, mark reads slot_of and the winners of claim. No kernel waits for
-// another workgroup. That is why hash and claim are two kernels: a claimant's row must be visible
-// to every lane that meets its claim.
+// Visibility is media_table.hpp's rule: claim reads the rows of hash and the stream, mark reads
+// slot_of and the winners of claim.
 #include "telemetry_dedupe.hpp"
 
 namespace {
@@ -86,16 +80,11 @@ __global__ __launch_bounds__(BLOCK) void dedupe_claim(const uint8_t* __restrict_
   const DedupeRow row = rows[m];
   if (row.len <= 0) return;
   const unsigned long long me = static_cast<unsigned long long>(m) + 1ull;
-  uint32_t slot = static_cast<uint32_t>(row.hash & hash_mask) & slot_mask;
-  for (;;) {  // ends: the contents are at most n, the slots at least 2n
-    // a claim is written once and never changes, so a non-zero value read here is final
-    unsigned long long owner = __hip_atomic_load(&claim[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (owner == 0) owner = atomicCAS(&claim[slot], 0ull, me);
-    if (owner == 0) break;  // claimed
-    const DedupeRow o = rows[owner - 1];  // a row with len > 0: only such lanes claim
-    if (o.len == row.len && o.hash == row.hash && content_equal<WIDE>(buf + o.off, buf + row.off, row.len)) break;
-    slot = (slot + 1) & slot_mask;
-  }
+  const auto same_content = [&](unsigned long long owner) {
+    const DedupeRow o = rows[owner];  // a row with len > 0: only such lanes claim
+    return o.len == row.len && o.hash == row.hash && content_equal<WIDE>(buf + o.off, buf + row.off, row.len);
+  };
+  const uint32_t slot = claim_slot(claim, slot_mask, home_slot(row.hash, hash_mask, slot_mask), me, same_content).slot;
   // n < 2^31; both values are in 1..n, so 0 stays "no frame"
   atomicMax(&winner[slot], first ? static_cast<uint32_t>(n - m) : static_cast<uint32_t>(me));
   slot_of[m] = static_cast<int32_t>(slot);

@@ -19,7 +19,7 @@
 // takes unaligned global addresses), and finishes the last 0-7 bytes one by one: it never reads a
 // byte outside the content, so there is no over-read to reason about at the end of the buffer.
 #pragma once
-#include "telemetry_readers.hpp"
+#include "media_table.hpp"
 
 namespace bh {
 
@@ -51,29 +51,26 @@ BH_FN uint64_t load8(const uint8_t* p) {
   return w;
 }
 
-// The fold's hash (FNV-1a, then murmur3's 64-bit finaliser) over the n bytes at p:
-// ops/gpu_dedupe.py frame_hash is the same. It only orders the probe; no result depends on it.
+// The fold's hash (media_table.hpp hash64_bytes) over the n bytes at p: ops/gpu_dedupe.py frame_hash
+// is the same. It only orders the probe; no result depends on it.
 template <bool WIDE>
 BH_FN uint64_t content_hash(const uint8_t* __restrict__ p, const int n) {
+  if (!WIDE) {
+    uint32_t high;
+    return hash64_bytes(p, n, high);
+  }
   uint64_t h = 0xcbf29ce484222325ull;
   int k = 0;
-  if (WIDE) {
-    for (; k + 8 <= n; k += 8) {
-      uint64_t w = load8(p + k);
-      BH_UNROLL
-      for (int j = 0; j < 8; ++j) {
-        h = (h ^ (w & 0xffu)) * 0x100000001b3ull;
-        w >>= 8;
-      }
+  for (; k + 8 <= n; k += 8) {
+    uint64_t w = load8(p + k);
+    BH_UNROLL
+    for (int j = 0; j < 8; ++j) {
+      h = (h ^ (w & 0xffu)) * 0x100000001b3ull;
+      w >>= 8;
     }
   }
   for (; k < n; ++k) h = (h ^ p[k]) * 0x100000001b3ull;
-  h ^= h >> 33;
-  h *= 0xff51afd7ed558ccdull;
-  h ^= h >> 33;
-  h *= 0xc4ceb9fe1a85ec53ull;
-  h ^= h >> 33;
-  return h;
+  return finalise64(h);
 }
 
 // Whether the n bytes at a and at b are equal. The two may overlap or be the same bytes.

@@ -19,19 +19,16 @@
 //    folded by the host with the service's codec, counters and all: an id with a byte >= 0x80
 //    (its identity is the decoded string, U+FFFD for invalid UTF-8, which the device does not
 //    model), and in the upb dialect a non-ASCII host (upb rejects invalid UTF-8) or a start-group.
-//  Pass B, fold_group, one lane per frame with the group flag. Open addressing over `slots`
-//    (a power of two, >= 2n) entries: the home slot is hash & hash_mask & (slots - 1), a lane
-//    claims an empty slot with a 64-bit compare-and-swap of m + 1, and where the slot is taken it
-//    compares length, hash and then the bytes of the claimant's id, so nothing depends on the
-//    hash being free of collisions. It moves to the next slot on a mismatch, wrapping at the end.
+//  Pass B, fold_group, one lane per frame with the group flag finds its id's slot in the group
+//    table (media_table.hpp claim_slot over `slots` entries, a power of two, >= 2n): ids are the
+//    same where length, hash and then the bytes are.
 //    Group updates: integer atomic adds for the three counts, and last-writer-wins by frame index,
 //    not by arrival, through an atomic max on (m + 1) << 32 | status. Every result is therefore the
 //    same from run to run.
 //
-// Visibility: within a launch workgroups meet only in atomics (the claims, the counts, the cursor).
-// Every plain load reads bytes written before the launch: buf, offs, and in pass B the rows of
+// Visibility is media_table.hpp's rule: in pass B every plain load reads buf, offs or the rows of
 // pass A. That is why the passes are two kernels and not one.
-#include "telemetry_readers.hpp"
+#include "media_table.hpp"
 
 namespace {
 
@@ -57,30 +54,6 @@ static_assert(N_COUNTERS == 72, "ops/gpu_fold.py allocates N_COUNTERS = 72 count
 
 constexpr int TOPIC_STATUS = 1, TOPIC_PROGRESS = 2;
 
-// FNV-1a over the bytes, then murmur3's 64-bit finaliser (ops/gpu_fold.py hash64 is the same)
-__device__ __forceinline__ uint64_t hash_bytes(const uint8_t* __restrict__ p, int n, uint32_t& high) {
-  uint64_t h = 0xcbf29ce484222325ull;
-  uint32_t any = 0;
-  for (int k = 0; k < n; ++k) {
-    const uint32_t b = p[k];
-    any |= b;
-    h = (h ^ b) * 0x100000001b3ull;
-  }
-  h ^= h >> 33;
-  h *= 0xff51afd7ed558ccdull;
-  h ^= h >> 33;
-  h *= 0xc4ceb9fe1a85ec53ull;
-  h ^= h >> 33;
-  high = any & 0x80u;
-  return h;
-}
-
-__device__ __forceinline__ bool has_high_byte(const uint8_t* __restrict__ p, int n) {
-  uint32_t any = 0;
-  for (int k = 0; k < n; ++k) any |= p[k];
-  return (any & 0x80u) != 0;
-}
-
 template <int DIALECT>
 __global__ __launch_bounds__(256) void fold_decode(const uint8_t* __restrict__ buf, const int32_t* __restrict__ offs,
                                                    int n, uint64_t known_mask, FoldRow* __restrict__ rows,
@@ -104,7 +77,7 @@ __global__ __launch_bounds__(256) void fold_decode(const uint8_t* __restrict__ b
       bool to_host = r.ok == OK_HOST;
       if (r.ok == OK_DECODED) {
         uint32_t high;
-        row.hash = hash_bytes(buf + r.id_off, r.id_len, high);
+        row.hash = hash64_bytes(buf + r.id_off, r.id_len, high);
         to_host = high != 0;
         if (DIALECT == DIALECT_UPB && !is_status && !to_host)
           to_host = has_high_byte(buf + r.host_off, r.host_len);
@@ -146,22 +119,11 @@ __global__ __launch_bounds__(256) void fold_group(const uint8_t* __restrict__ bu
   const FoldRow row = rows[m];
   if (!(row.flags & F_GROUP)) return;
   const unsigned long long me = static_cast<unsigned long long>(m) + 1ull;
-  uint32_t slot = static_cast<uint32_t>(row.hash & hash_mask) & slot_mask;
-  for (;;) {  // ends: the groups are at most n, the slots at least 2n
-    // a claim is written once and never changes, so a non-zero value read here is final
-    unsigned long long owner = __hip_atomic_load(&claim[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (owner == 0) owner = atomicCAS(&claim[slot], 0ull, me);
-    if (owner == 0) break;  // claimed
-    const FoldRow o = rows[owner - 1];
-    if (o.id_len == row.id_len && o.hash == row.hash) {
-      const uint8_t* __restrict__ a = buf + o.id_off;
-      const uint8_t* __restrict__ b = buf + row.id_off;
-      int k = 0;
-      while (k < row.id_len && a[k] == b[k]) ++k;
-      if (k == row.id_len) break;  // the same id
-    }
-    slot = (slot + 1) & slot_mask;
-  }
+  const auto same_id = [&](unsigned long long owner) {
+    const FoldRow o = rows[owner];
+    return o.id_len == row.id_len && o.hash == row.hash && bytes_equal(buf + o.id_off, buf + row.id_off, row.id_len);
+  };
+  const uint32_t slot = claim_slot(claim, slot_mask, home_slot(row.hash, hash_mask, slot_mask), me, same_id).slot;
   if (row.flags & F_STATUS) {
     atomicAdd(&counts[3 * slot], 1u);
     atomicMax(&last[slot], (me << 32) | static_cast<uint32_t>(row.status));

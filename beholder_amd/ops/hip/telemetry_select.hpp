@@ -15,10 +15,10 @@
 //
 // The media table is built on the host (ops/gpu_extract.py build_media_table) from the ASCII query
 // ids: open addressing over `slot_mask + 1` entries, a power of two of at least twice the ids, so an
-// empty entry always ends a probe chain. The home slot is hash & hash_mask & slot_mask. A hit is
+// empty entry always ends a probe chain. The hash and the home slot are media_table.hpp's. A hit is
 // decided by length, hash and then the bytes, never by the hash alone.
 #pragma once
-#include "telemetry_readers.hpp"
+#include "media_table.hpp"
 
 namespace bh {
 
@@ -52,44 +52,14 @@ struct MediaEntry {
 };
 static_assert(sizeof(MediaEntry) == 16, "ops/gpu_extract.py builds the table as 16-byte entries");
 
-// FNV-1a over the bytes, then murmur3's 64-bit finaliser: the fold's hash (ops/gpu_fold.py hash64).
-// `high` is non-zero where a byte is >= 0x80.
-BH_FN uint64_t hash_id(const uint8_t* __restrict__ p, int n, uint32_t& high) {
-  uint64_t h = 0xcbf29ce484222325ull;
-  uint32_t any = 0;
-  for (int k = 0; k < n; ++k) {
-    const uint32_t b = p[k];
-    any |= b;
-    h = (h ^ b) * 0x100000001b3ull;
-  }
-  h ^= h >> 33;
-  h *= 0xff51afd7ed558ccdull;
-  h ^= h >> 33;
-  h *= 0xc4ceb9fe1a85ec53ull;
-  h ^= h >> 33;
-  high = any & 0x80u;
-  return h;
-}
-
-BH_FN bool any_high_byte(const uint8_t* __restrict__ p, int n) {
-  uint32_t any = 0;
-  for (int k = 0; k < n; ++k) any |= p[k];
-  return (any & 0x80u) != 0;
-}
-
 // Is the id p[0, n) with this hash in the table? Ends at the first empty entry.
 BH_FN bool table_has(const MediaEntry* __restrict__ table, const uint8_t* __restrict__ blob, const SelectParams& s,
                      const uint8_t* __restrict__ p, int n, uint64_t hash) {
-  uint32_t slot = static_cast<uint32_t>(hash & s.hash_mask) & s.slot_mask;
+  uint32_t slot = home_slot(hash, s.hash_mask, s.slot_mask);
   for (;;) {
     const MediaEntry e = table[slot];
     if (e.len < 0) return false;
-    if (e.len == n && e.hash == hash) {
-      const uint8_t* __restrict__ q = blob + e.off;
-      int k = 0;
-      while (k < n && q[k] == p[k]) ++k;
-      if (k == n) return true;
-    }
+    if (e.len == n && e.hash == hash && bytes_equal(blob + e.off, p, n)) return true;
     slot = (slot + 1) & s.slot_mask;
   }
 }
@@ -109,9 +79,9 @@ BH_FN int decide(const uint8_t* __restrict__ buf, const int head, const int end,
     if (r.ok == OK_HOST) return DECIDE_HOST;
     if (r.ok == OK_DECODED) {
       uint32_t high;
-      hash = hash_id(buf + r.id_off, r.id_len, high);
+      hash = hash64_bytes(buf + r.id_off, r.id_len, high);
       if (high) return DECIDE_HOST;
-      if (DIALECT == DIALECT_UPB && !is_status && any_high_byte(buf + r.host_off, r.host_len)) return DECIDE_HOST;
+      if (DIALECT == DIALECT_UPB && !is_status && has_high_byte(buf + r.host_off, r.host_len)) return DECIDE_HOST;
       outcome = OUT_DECODED;
     } else {
       outcome = OUT_ERROR;

@@ -11,8 +11,8 @@
 // answer does not depend on what it holds (another topic; every frame where one shard takes the
 // undecoded ones too) is not read at all, so it never goes to the host.
 //
-// The shard of a decoded frame is the high half of the fold's hash of its id bytes (hash_id of
-// telemetry_select.hpp), scaled to [0, shards) by one 32 x 32 -> 64 bit multiply and a shift:
+// The shard of a decoded frame is the high half of the fold's hash of its id bytes (hash64_bytes of
+// media_table.hpp), scaled to [0, shards) by one 32 x 32 -> 64 bit multiply and a shift:
 // shard.shard_of is the same.
 #pragma once
 #include "telemetry_select.hpp"
@@ -48,9 +48,9 @@ BH_FN int route(const uint8_t* __restrict__ buf, const int head, const int end, 
   if (r.ok == OK_HOST) return ROUTE_HOST;
   if (r.ok != OK_DECODED) return undecoded;
   uint32_t high;
-  const uint64_t hash = hash_id(buf + r.id_off, r.id_len, high);
+  const uint64_t hash = hash64_bytes(buf + r.id_off, r.id_len, high);
   if (high) return ROUTE_HOST;
-  if (DIALECT == DIALECT_UPB && !is_status && any_high_byte(buf + r.host_off, r.host_len)) return ROUTE_HOST;
+  if (DIALECT == DIALECT_UPB && !is_status && has_high_byte(buf + r.host_off, r.host_len)) return ROUTE_HOST;
   return shard_of_hash(hash, s.shards);
 }
 

@@ -47,8 +47,8 @@ BH_FN int thin_classify(const uint8_t* __restrict__ buf, const int head, const i
   int kind = r.ok == OK_HOST ? TH_HOST : r.ok == OK_DECODED ? TH_EVENT : TH_ERROR;
   if (kind == TH_EVENT) {
     uint32_t high;
-    const uint64_t hash = hash_id(buf + r.id_off, r.id_len, high);
-    if (high || (DIALECT == DIALECT_UPB && any_high_byte(buf + r.host_off, r.host_len))) {
+    const uint64_t hash = hash64_bytes(buf + r.id_off, r.id_len, high);
+    if (high || (DIALECT == DIALECT_UPB && has_high_byte(buf + r.host_off, r.host_len))) {
       kind = TH_HOST;
     } else {
       ev.hash = hash;

@@ -14,9 +14,9 @@
 //    (telemetry_transitions.hpp classify, upb in its STRICT form): the lane counts the decode error,
 //    or hands the frame to the host through the overflow list with its atomic cursor, or writes the
 //    event's row {hash, id_off, id_len, status} and is_event[m] = 1. Other topics are not read.
-//  claim, tr_claim, one lane per status event: the fold's open-addressing table over `slots`
-//    entries (a power of two, >= 2n; home slot hash & hash_mask & (slots - 1); 64-bit
-//    compare-and-swap of m + 1; length, hash and then the bytes of the claimant's id compared).
+//  claim, tr_claim, one lane per status event finds its id's slot in the fold's table
+//    (media_table.hpp claim_slot over `slots` entries, a power of two, >= 2n): ids are the same
+//    where length, hash and then the bytes are.
 //    Every event learns its slot, slot_of[m]; the claimant also sets slot_used[slot].
 //  rank and compact are the extract's scan (telemetry_select.hip bh_select_scan) called as it is,
 //    over slot_used (a claimed slot's rank is its dense media number in [0, groups)) and over
@@ -46,10 +46,8 @@
 //    media's first or last word and the run's bound with plain stores: each has exactly one writer.
 //    The position before a block's first is read from global memory like any other.
 //
-// Visibility is the fold's rule: within a launch workgroups meet only in atomics (the claims, the
-// cursor, the counts); every plain load reads what an earlier launch or the host wrote. No kernel
-// waits for another workgroup. Every lane's loops are bounded by the frame's own length or by the
-// table's size.
+// Visibility is media_table.hpp's rule. Every lane's loops are bounded by the frame's own length or
+// by the table's size.
 #include "block_scan.hpp"
 #include "telemetry_transitions.hpp"
 
@@ -99,28 +97,13 @@ __global__ __launch_bounds__(BLOCK) void tr_claim(const uint8_t* __restrict__ bu
   const StatusEvent row = rows[m];
   if (row.kind != TR_EVENT) return;
   const unsigned long long me = static_cast<unsigned long long>(m) + 1ull;
-  uint32_t slot = static_cast<uint32_t>(row.hash & hash_mask) & slot_mask;
-  // the groups are at most n and the slots at least 2n, so an empty slot or the id's own is met
-  // before the table has been walked once; the bound only says so to the reader
-  for (uint32_t walked = 0; walked <= slot_mask; ++walked) {
-    // a claim is written once and never changes, so a non-zero value read here is final
-    unsigned long long owner = __hip_atomic_load(&claim[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (owner == 0) owner = atomicCAS(&claim[slot], 0ull, me);
-    if (owner == 0) {  // claimed: the one writer of slot_used[slot]
-      slot_used[slot] = 1;
-      break;
-    }
-    const StatusEvent o = rows[owner - 1];
-    if (o.id_len == row.id_len && o.hash == row.hash) {
-      const uint8_t* __restrict__ a = buf + o.id_off;
-      const uint8_t* __restrict__ b = buf + row.id_off;
-      int k = 0;
-      while (k < row.id_len && a[k] == b[k]) ++k;
-      if (k == row.id_len) break;  // the same id
-    }
-    slot = (slot + 1) & slot_mask;
-  }
-  slot_of[m] = slot;
+  const auto same_id = [&](unsigned long long owner) {
+    const StatusEvent o = rows[owner];
+    return o.id_len == row.id_len && o.hash == row.hash && bytes_equal(buf + o.id_off, buf + row.id_off, row.id_len);
+  };
+  const Claim c = claim_slot(claim, slot_mask, home_slot(row.hash, hash_mask, slot_mask), me, same_id);
+  if (c.claimed) slot_used[c.slot] = 1;  // the one writer of slot_used[slot]
+  slot_of[m] = c.slot;
 }
 
 // event k: frame[k] is its frame (the event scan's indices), slot_rank[slot] >> 32 its slot's rank

@@ -23,7 +23,7 @@ constexpr uint32_t CLASS_UNKNOWN = 64;
 constexpr uint32_t CLASSES = 65;  // 0-63 and CLASS_UNKNOWN: the matrix is CLASSES x CLASSES
 
 struct StatusEvent {
-  uint64_t hash;   // hash_id of the id bytes
+  uint64_t hash;   // hash64_bytes of the id bytes
   int32_t id_off;  // absolute in buf
   int32_t id_len;
   int32_t status;
@@ -46,7 +46,7 @@ BH_FN int classify(const uint8_t* __restrict__ buf, const int head, const int en
   int kind = r.ok == OK_HOST ? TR_HOST : r.ok == OK_DECODED ? TR_EVENT : TR_ERROR;
   if (kind == TR_EVENT) {
     uint32_t high;
-    ev.hash = hash_id(buf + r.id_off, r.id_len, high);
+    ev.hash = hash64_bytes(buf + r.id_off, r.id_len, high);
     if (high) {
       kind = TR_HOST;
       ev.hash = 0;

@@ -1,7 +1,8 @@
 """The gfx950 extension (``ops/hip/libbeholder_hip.so``) as Python sees it: where it lies, how it is
-loaded, and the argument checks its callers share (``ops/gpu_decode.py``, ``ops/gpu_fold.py``,
-``ops/gpu_extract.py``, ``ops/gpu_coalesce.py``, ``ops/gpu_shard.py``, ``ops/gpu_dedupe.py``,
-``ops/gpu_transitions.py``, ``ops/gpu_thin.py``).
+loaded, and what its callers share: the launch helper, the argument checks and the reader of the
+overflow list (``ops/gpu_decode.py``, ``ops/gpu_fold.py``, ``ops/gpu_extract.py``,
+``ops/gpu_coalesce.py``, ``ops/gpu_shard.py``, ``ops/gpu_dedupe.py``, ``ops/gpu_transitions.py``,
+``ops/gpu_thin.py``).
 
 The library is built in-tree by ``beholder_amd._build.build_hip`` (hipcc, gfx950) and loaded with
 ctypes after ``import torch``. torch's HIP runtime has the same soname, so the kernels launch on
@@ -14,6 +15,7 @@ import os
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hip", "libbeholder_hip.so")
 DIALECT_IDS = {"upb": 0, "protobufjs": 1}  # DIALECT_* of hip/telemetry_readers.hpp
+ALL_ONES = 0xFFFFFFFFFFFFFFFF
 _lib = None
 
 
@@ -27,7 +29,7 @@ def lib() -> ctypes.CDLL:
         import torch  # noqa: F401  load torch's libamdhip64 first so the kernels share its runtime
         so = ctypes.CDLL(LIB_PATH)
         p, i = ctypes.c_void_p, ctypes.c_int
-        so.bh_decode_telemetry.argtypes = [p, p, i, p, p, i]
+        so.bh_decode_telemetry.argtypes = [p, p, i, p, i, p]
         so.bh_decode_telemetry.restype = i
         so.bh_fold_telemetry.argtypes = [p, p, i, i, ctypes.c_ulonglong, ctypes.c_ulonglong] + [p] * 6 + \
                                         [ctypes.c_longlong, i, p]
@@ -70,6 +72,35 @@ def lib() -> ctypes.CDLL:
     return _lib
 
 
+def call(name: str, anchor, *args) -> None:
+    """Launches entry point ``name`` with ``args`` and, as its last argument, the current torch
+    stream of ``anchor``'s device (a tensor the kernels read or write). ``RuntimeError`` for a
+    ``hipError_t`` that is not 0."""
+    import torch
+    entry = getattr(lib(), name)
+    with torch.cuda.device(anchor.device):
+        err = entry(*args, torch.cuda.current_stream().cuda_stream)
+    if err:
+        raise RuntimeError(f"{name} launch failed: hipError {err}")
+
+
+def require_gpu(device, what: str) -> None:
+    """``ValueError`` where ``device`` is no GPU; ``what`` names the entry point."""
+    import torch
+    if torch.device(device).type != "cuda":
+        raise ValueError(f"{what} needs a GPU device, not {device!r}")
+
+
+def check_hash_mask(hash_mask) -> int:
+    """The 64-bit mask the kernels AND onto every hash: all ones for ``None``, else an ``int`` (no
+    ``bool``) in ``0 .. 2**64 - 1``."""
+    if hash_mask is None:
+        return ALL_ONES
+    if isinstance(hash_mask, bool) or not isinstance(hash_mask, int) or not 0 <= hash_mask <= ALL_ONES:
+        raise ValueError("hash_mask is 64-bit")
+    return hash_mask
+
+
 def check_dialect(dialect: str) -> int:
     """The kernels' number for ``dialect``; ``ValueError`` for one they do not read."""
     if dialect not in DIALECT_IDS:
@@ -86,3 +117,28 @@ def check_device_tensors(buf_dev, offs_dev, n: int) -> None:
     if not (buf_dev.is_cuda and offs_dev.is_cuda and buf_dev.is_contiguous() and offs_dev.is_contiguous()
             and buf_dev.device == offs_dev.device):
         raise ValueError("the kernels need contiguous tensors on one device")
+
+
+def check_stream(buf_dev, offs_dev, n: int, what: str) -> None:
+    """What every command over a framed stream needs before it allocates: :func:`check_device_tensors`,
+    at least one frame, and a stream that int32 offsets reach. ``what`` names the command."""
+    check_device_tensors(buf_dev, offs_dev, n)
+    if n < 1:
+        raise ValueError(f"{what} needs n >= 1")
+    if buf_dev.numel() >= 2 ** 31:
+        raise ValueError("stream too large for int32 offsets")
+
+
+def overflow_frames(overflow, count: int, data, offs):
+    """The frames the device left to the host: ``(frames, events)``, the first ``count`` entries of
+    the device's ``overflow`` list as a sorted int array, and an iterator of ``(frame, topic, body)``
+    over them from the host's own copy of the stream."""
+    import numpy as np
+    frames = np.sort(overflow[:count].cpu().numpy())
+    view = memoryview(data)
+
+    def events():
+        for i in frames.tolist():
+            a, b = int(offs[i]), int(offs[i + 1])
+            yield i, view[a + 4], bytes(view[a + 5:b])
+    return frames, events()

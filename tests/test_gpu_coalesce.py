@@ -111,6 +111,28 @@ def test_forced_collisions_stay_exact(hash_mask, policy):
         assert len(want.indices) > 240
 
 
+def test_probing_wraps_at_the_end_of_the_table():
+    """64 ids chosen so that, under the mask slots - 1, each status key's home is among the last eight
+    of the table's 256 slots: 64 keys do not fit into eight slots, so chains run off the end and go on
+    from slot 0."""
+    slots = gpu_fold.table_slots(128)
+    assert slots == 256
+    ids, k = [], 0
+    while len(ids) < 64:
+        mid = b"w%d" % k
+        k += 1
+        if gc.key_hash(mid, STATUS_ID) & (slots - 1) >= slots - 8:
+            ids.append(mid)
+    homes = {gc.key_hash(mid, STATUS_ID) & (slots - 1) for mid in ids}
+    assert len(ids) > 8 >= len(homes) and min(homes) >= slots - 8  # more keys than slots up to the end: a chain wraps
+    rng = random.Random(2)
+    events = [(STATUS_ID, _body(mid, rng.randrange(6))) for mid in ids for _ in range(2)]
+    rng.shuffle(events)
+    want, host_frames = _same(frames(events), hash_mask=slots - 1)
+    assert host_frames == 0 and want.frames == 128 and len(want.indices) == 64
+    assert {key[1] for key in want.keys} == {mid.decode() for mid in ids}
+
+
 @pytest.mark.parametrize("dialect", ops.DIALECTS)
 @pytest.mark.parametrize("policy", POLICIES, ids=policy_id)
 def test_fold_corpus(policy, dialect):

@@ -144,6 +144,29 @@ def test_every_key_in_one_probe_chain():
     _same(pairs_stream(), hash_mask=0xFF, public=False)
 
 
+def test_probing_wraps_at_the_end_of_the_table():
+    """64 ids chosen so that, under the mask slots - 1, each one's home is among the last eight of the
+    table's 256 slots: 64 media do not fit into eight slots, so chains run off the end and go on from
+    slot 0."""
+    slots = gpu_fold.table_slots(128)
+    assert slots == 256
+    ids, k = [], 0
+    while len(ids) < 64:
+        mid = b"w%d" % k
+        k += 1
+        if gpu_fold.hash64(mid) & (slots - 1) >= slots - 8:
+            ids.append(mid)
+    homes = {gpu_fold.hash64(mid) & (slots - 1) for mid in ids}
+    assert len(ids) > 8 >= len(homes) and min(homes) >= slots - 8  # more media than slots up to the end: a chain wraps
+    rng = random.Random(2)
+    events = [(STATUS_ID, _body(mid, rng.randrange(6))) for mid in ids for _ in range(2)]
+    rng.shuffle(events)
+    want, host_frames = _same(frames(events), hash_mask=slots - 1)
+    assert host_frames == 0 and want.frames == want.status_events == 128
+    assert set(want.media) == {mid.decode() for mid in ids}
+    assert all(flow.status_events == 2 for flow in want.media.values())
+
+
 @pytest.mark.parametrize("dialect", ops.DIALECTS)
 def test_fold_corpus(dialect):
     want, host_frames = _same(_corpus(), dialect)
