@@ -8,6 +8,7 @@ gen      write synthetic framed telemetry to stdout/a file (+ optional media fix
 decode   turn a framed stream into NDJSON (debugging).
 summarise  fold a framed stream into its end state: counters, comments, final statuses (``replay``).
 transitions  count a framed stream's per-media status moves: the transition matrix, changes, repeats (``transitions``).
+hosts    what every worker host did in a framed stream: events, media, stints, handovers, what it held (``hosts``).
 extract  cut a framed stream down to selected frames, a framed stream again (``extract``).
 dedupe   drop the byte-identical repeat frames of a framed stream, a framed stream again (``dedupe``).
 thin     drop the progress events that repeat their media's step, a framed stream again (``thin``).
@@ -292,6 +293,34 @@ def cmd_transitions(a: argparse.Namespace) -> int:
         source = a.input if a.input else io.BytesIO(sys.stdin.buffer.read())
         result, host_frames = transitions.transitions_file(source, device=a.device, dialect=a.dialect,
                                                            chunk_bytes=a.chunk_bytes)
+    except ValueError as e:
+        print(f"beholder: {e}", file=sys.stderr)
+        return 1
+    out = result.to_json(per_media=a.per_media)
+    out["host_frames"] = host_frames
+    print(json.dumps(out))
+    return 0
+
+
+def cmd_hosts(a: argparse.Namespace) -> int:
+    """What every worker host did in this stream, and what it held at the end (``beholder_amd.hosts``)."""
+    import io
+
+    from . import hosts
+    if a.device == "gpu":
+        try:
+            import torch
+
+            from .ops import gpu_hosts, hip_lib  # noqa: F401  gpu_hosts: its imports fail here, not mid-run
+            if not torch.cuda.is_available():
+                raise RuntimeError("no GPU is visible")
+            hip_lib.lib()
+        except (ImportError, RuntimeError, OSError) as e:
+            print(f"beholder: --device gpu is not available ({e}); use --device cpu", file=sys.stderr)
+            return 1
+    try:
+        source = a.input if a.input else io.BytesIO(sys.stdin.buffer.read())
+        result, host_frames = hosts.hosts_file(source, device=a.device, dialect=a.dialect, chunk_bytes=a.chunk_bytes)
     except ValueError as e:
         print(f"beholder: {e}", file=sys.stderr)
         return 1
@@ -660,6 +689,18 @@ def build_parser() -> argparse.ArgumentParser:
     t.add_argument("--chunk-bytes", type=int, default=256 << 20, help="read the input in pieces of this size")
     t.add_argument("--per-media", action="store_true", help="also print one row per mediaId")
     t.set_defaults(fn=cmd_transitions)
+
+    w = sub.add_parser("hosts", help="framed stream -> what every worker host did in it (JSON)",
+                       description="Count, per worker host of the progress events, its events, media, stints, "
+                                   "the media it took over and lost, its rewinds, and the media it held when the "
+                                   "stream ended, by status. Prints one JSON object.")
+    w.add_argument("input", nargs="?")
+    w.add_argument("--device", choices=["cpu", "gpu"], default="cpu",
+                   help="cpu: the definition, runs anywhere; gpu: the gfx950 hosts kernels")
+    w.add_argument("--dialect", choices=["protobufjs", "upb"], default="protobufjs")
+    w.add_argument("--chunk-bytes", type=int, default=256 << 20, help="read the input in pieces of this size")
+    w.add_argument("--per-media", action="store_true", help="also print one row per mediaId")
+    w.set_defaults(fn=cmd_hosts)
 
     x = sub.add_parser("extract", help="framed stream -> the selected frames, a framed stream again",
                        description="Keep the frames that meet every given condition (none: all frames); "

@@ -2,7 +2,7 @@
 loaded, and what its callers share: the launch helper, the argument checks and the reader of the
 overflow list (``ops/gpu_decode.py``, ``ops/gpu_fold.py``, ``ops/gpu_extract.py``,
 ``ops/gpu_coalesce.py``, ``ops/gpu_shard.py``, ``ops/gpu_dedupe.py``, ``ops/gpu_transitions.py``,
-``ops/gpu_thin.py``).
+``ops/gpu_thin.py``, ``ops/gpu_hosts.py``).
 
 The library is built in-tree by ``beholder_amd._build.build_hip`` (hipcc, gfx950) and loaded with
 ctypes after ``import torch``. torch's HIP runtime has the same soname, so the kernels launch on
@@ -68,6 +68,15 @@ def lib() -> ctypes.CDLL:
         so.bh_thin_classify.restype = i
         so.bh_thin_mark.argtypes = [p, p, i, i, i] + [p] * 4
         so.bh_thin_mark.restype = i
+        # telemetry_hosts.hip (ops/gpu_hosts.py): classify, number, pairs, walk
+        so.bh_hosts_classify.argtypes = [p, p, i, i] + [p] * 7
+        so.bh_hosts_classify.restype = i
+        so.bh_hosts_number.argtypes = [p, i, i, p, p, ctypes.c_longlong] + [p] * 4
+        so.bh_hosts_number.restype = i
+        so.bh_hosts_pairs.argtypes = [p, p, i, ctypes.c_ulonglong, p, p, p, ctypes.c_longlong, p]
+        so.bh_hosts_pairs.restype = i
+        so.bh_hosts_walk.argtypes = [p, p, p, p, i, i, i, ctypes.c_ulonglong] + [p] * 4
+        so.bh_hosts_walk.restype = i
         _lib = so
     return _lib
 
