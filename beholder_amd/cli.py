@@ -9,6 +9,7 @@ decode   turn a framed stream into NDJSON (debugging).
 summarise  fold a framed stream into its end state: counters, comments, final statuses (``replay``).
 transitions  count a framed stream's per-media status moves: the transition matrix, changes, repeats (``transitions``).
 hosts    what every worker host did in a framed stream: events, media, stints, handovers, what it held (``hosts``).
+stages   join both topics of a framed stream per media: what stage each is in and how far (``stages``).
 extract  cut a framed stream down to selected frames, a framed stream again (``extract``).
 dedupe   drop the byte-identical repeat frames of a framed stream, a framed stream again (``dedupe``).
 thin     drop the progress events that repeat their media's step, a framed stream again (``thin``).
@@ -321,6 +322,34 @@ def cmd_hosts(a: argparse.Namespace) -> int:
     try:
         source = a.input if a.input else io.BytesIO(sys.stdin.buffer.read())
         result, host_frames = hosts.hosts_file(source, device=a.device, dialect=a.dialect, chunk_bytes=a.chunk_bytes)
+    except ValueError as e:
+        print(f"beholder: {e}", file=sys.stderr)
+        return 1
+    out = result.to_json(per_media=a.per_media)
+    out["host_frames"] = host_frames
+    print(json.dumps(out))
+    return 0
+
+
+def cmd_stages(a: argparse.Namespace) -> int:
+    """Both topics of this stream joined per media: the stage every media is in and how far (``beholder_amd.stages``)."""
+    import io
+
+    from . import stages
+    if a.device == "gpu":
+        try:
+            import torch
+
+            from .ops import gpu_stages, hip_lib  # noqa: F401  gpu_stages: its imports fail here, not mid-run
+            if not torch.cuda.is_available():
+                raise RuntimeError("no GPU is visible")
+            hip_lib.lib()
+        except (ImportError, RuntimeError, OSError) as e:
+            print(f"beholder: --device gpu is not available ({e}); use --device cpu", file=sys.stderr)
+            return 1
+    try:
+        source = a.input if a.input else io.BytesIO(sys.stdin.buffer.read())
+        result, host_frames = stages.stages_file(source, device=a.device, dialect=a.dialect, chunk_bytes=a.chunk_bytes)
     except ValueError as e:
         print(f"beholder: {e}", file=sys.stderr)
         return 1
@@ -701,6 +730,19 @@ def build_parser() -> argparse.ArgumentParser:
     w.add_argument("--chunk-bytes", type=int, default=256 << 20, help="read the input in pieces of this size")
     w.add_argument("--per-media", action="store_true", help="also print one row per mediaId")
     w.set_defaults(fn=cmd_hosts)
+
+    g = sub.add_parser("stages", help="framed stream -> what stage each media is in and how far (JSON)",
+                       description="Join the status and the progress events per media: the status events per "
+                                   "class, the progress events by standing and reported status, the closed and the "
+                                   "open stages by status and progress bucket, and the progress events that come "
+                                   "before their media's first status event. Prints one JSON object.")
+    g.add_argument("input", nargs="?")
+    g.add_argument("--device", choices=["cpu", "gpu"], default="cpu",
+                   help="cpu: the definition, runs anywhere; gpu: the gfx950 stages kernels")
+    g.add_argument("--dialect", choices=["protobufjs", "upb"], default="protobufjs")
+    g.add_argument("--chunk-bytes", type=int, default=256 << 20, help="read the input in pieces of this size")
+    g.add_argument("--per-media", action="store_true", help="also print one row per mediaId")
+    g.set_defaults(fn=cmd_stages)
 
     x = sub.add_parser("extract", help="framed stream -> the selected frames, a framed stream again",
                        description="Keep the frames that meet every given condition (none: all frames); "

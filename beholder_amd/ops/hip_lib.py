@@ -2,7 +2,7 @@
 loaded, and what its callers share: the launch helper, the argument checks and the reader of the
 overflow list (``ops/gpu_decode.py``, ``ops/gpu_fold.py``, ``ops/gpu_extract.py``,
 ``ops/gpu_coalesce.py``, ``ops/gpu_shard.py``, ``ops/gpu_dedupe.py``, ``ops/gpu_transitions.py``,
-``ops/gpu_thin.py``, ``ops/gpu_hosts.py``).
+``ops/gpu_thin.py``, ``ops/gpu_hosts.py``, ``ops/gpu_stages.py``).
 
 The library is built in-tree by ``beholder_amd._build.build_hip`` (hipcc, gfx950) and loaded with
 ctypes after ``import torch``. torch's HIP runtime has the same soname, so the kernels launch on
@@ -77,6 +77,13 @@ def lib() -> ctypes.CDLL:
         so.bh_hosts_pairs.restype = i
         so.bh_hosts_walk.argtypes = [p, p, p, p, i, i, i, ctypes.c_ulonglong] + [p] * 4
         so.bh_hosts_walk.restype = i
+        # telemetry_stages.hip (ops/gpu_stages.py): classify, carry, settle
+        so.bh_stages_classify.argtypes = [p, p, i, i] + [p] * 6
+        so.bh_stages_classify.restype = i
+        so.bh_stages_carry.argtypes = [p, p, i, i] + [p] * 8
+        so.bh_stages_carry.restype = i
+        so.bh_stages_settle.argtypes = [p] * 6 + [i, i, ctypes.c_ulonglong] + [p] * 4
+        so.bh_stages_settle.restype = i
         _lib = so
     return _lib
 
