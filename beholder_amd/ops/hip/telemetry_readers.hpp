@@ -30,7 +30,9 @@
 //        the next end-group tag of any field (counted, not recursed), wire types 4/6/7 fail.
 //  * DIALECT_UPB (google.protobuf's rules, the tooling oracle): last value wins, unknown fields
 //    of wire types 0/1/2/5 are skipped, a known field with an unexpected wire type is skipped
-//    like an unknown one, field 0, truncation or wire types 3/4/6/7 set ok = OK_ERROR.
+//    like an unknown one, field 0, truncation or wire types 3/4/6/7 set ok = OK_ERROR. A tag is a
+//    varint of up to 10 bytes and its field number is all of key >> 3, up to 61 bits: a number
+//    past 32 bits is an unknown field whatever its low 32 bits say.
 //    With STRICT the reader follows ops/csrc/wire.hpp to the letter where the plain one is
 //    looser: a tag is a varint of at most 5 bytes whose value fits 32 bits, and a start-group
 //    (which wire.hpp skips with a stack of field numbers) sets ok = OK_HOST: the caller hands
@@ -106,7 +108,13 @@ BH_FN void decode_upb(const uint8_t* __restrict__ buf, int i, const int end, Row
   while (i < end) {
     uint64_t key;
     if (STRICT ? !read_tag_strict(buf, end, i, key) : !read_varint(buf, end, i, key)) { r.ok = OK_ERROR; return; }
-    const uint32_t field = static_cast<uint32_t>(key >> 3), wt = static_cast<uint32_t>(key & 7);
+    uint32_t field = static_cast<uint32_t>(key >> 3);
+    const uint32_t wt = static_cast<uint32_t>(key & 7);
+    // The field number is the whole key >> 3: 2^32 + 1 is an unknown field, not mediaId, and 2^32 is
+    // not field 0. A STRICT key fits 32 bits already, so its code stays as it was.
+    if constexpr (!STRICT) {
+      if (key >> 35) field = 0xffffffffu;  // stands for every number past 32 bits: known to no message
+    }
     if (field == 0) { r.ok = OK_ERROR; return; }
     if (wt == 0) {
       uint64_t v;

@@ -92,6 +92,7 @@ struct Conn {  // the loop's side of one job
   Job* job;
   int peer;
   int sent;
+  bool spare;  // never closed at random: a starved job that only its deadline can end
 };
 
 int main() {
@@ -137,7 +138,10 @@ int main() {
       j->need = 1 + int(rng() % 3);
       bool starve = rng() % 10 == 0;  // never fed: the deadline scan must end it
       j->deadline = beholder::reactor_now() + (starve ? 0.02 : 60.0);
-      live.push_back({j, sv[1], starve ? 1 << 20 : 0});
+      // The loop closes a connection within some 400 passes, which takes less than the 20 ms of a
+      // starved job's deadline unless the machine is slow. Every other starved job is therefore
+      // spared, so that the expiry path runs on any machine; the rest still race the close.
+      live.push_back({j, sv[1], starve ? 1 << 20 : 0, starve && rng() % 2 == 0});
       if (!reactor.submit(j)) {
         std::fprintf(stderr, "submit failed\n");
         return 1;
@@ -157,7 +161,7 @@ int main() {
           char b = 'x';
           if (::send(c.peer, &b, 1, MSG_NOSIGNAL) == 1) ++c.sent;
         }
-        if (rng() % 400 == 0) {  // the connection closes while its handshake runs (or just ended)
+        if (!c.spare && rng() % 400 == 0) {  // the connection closes while its handshake runs (or just ended)
           Job* x = c.job;
           int fd = x->fd;
           c.job = nullptr;

@@ -23,6 +23,7 @@ from beholder_amd.transport.framing import iter_frames
 
 np = pytest.importorskip("numpy")
 from beholder_amd.ops import gpu_coalesce as gc  # noqa: E402
+import wire_edges  # noqa: E402
 from coalesce_cases import POLICIES, mixed_stream, policy_id  # noqa: E402
 from telemetry_corpus import fold_corpus  # noqa: E402
 
@@ -127,6 +128,21 @@ def test_the_host_set_is_the_rules_and_shrinks_with_what_is_read(program, tmp_pa
                 PROGRESS_ID: not (policy.progress == "all" and policy.undecoded == "keep"
                                   or policy.progress == "none" and policy.undecoded == "drop")}
         assert host == {i for i in default if read[events[i][0]]}, policy
+
+
+@pytest.mark.parametrize("dialect", ops.DIALECTS)
+@pytest.mark.parametrize("policy", [Policy(), Policy("last", "per-status", "drop")], ids=policy_id)
+def test_the_decision_agrees_with_the_definition_on_the_wire_edges(program, tmp_path, policy, dialect):
+    """Both policies read both topics; the second keys a progress by its status too."""
+    stream = wire_edges.stream()
+    got = _decisions(program, dialect, stream, policy, tmp_path)
+    host = _against_the_definition(stream, got, policy, dialect)
+    print(f"{dialect}: {len(got)} frames, {len(host)} left to the host")
+    assert len(got) == 2 * len(wire_edges.bodies()) and sum(words[0] == "key" for words in got) > 4000
+    assert len(host) <= wire_edges.HOST_CAP[dialect] * len(got)
+    if dialect == "protobufjs":
+        want = wire_edges.expected(dialect)
+        assert host == {i for i, v in enumerate(want) if v is not None and not v.media_id.isascii()}
 
 
 @pytest.mark.parametrize("dialect", ops.DIALECTS)

@@ -20,6 +20,7 @@ from beholder_amd.transport.framing import iter_frames
 
 np = pytest.importorskip("numpy")  # gpu_fold imports it
 from beholder_amd.ops import gpu_fold  # noqa: E402
+import wire_edges  # noqa: E402
 from hosts_cases import (corpus, many_workers, non_ascii_stream, random_stream, shared_by_worker_stream,  # noqa: E402
                          stitch_stream)
 from thin_cases import edge_stream, mixed_stream  # noqa: E402
@@ -110,6 +111,18 @@ def test_the_lines_agree_with_the_definition_on_the_fold_corpus(program, tmp_pat
     assert kinds["skip"] == {i for i, (topic, _) in enumerate(iter_frames(stream)) if topic != PROGRESS_ID}
     if dialect == "protobufjs":
         assert kinds["host"] == _rule(stream) and len(kinds["host"]) == 127
+
+
+@pytest.mark.parametrize("dialect", ops.DIALECTS)
+def test_the_lines_agree_with_the_definition_on_the_wire_edges(program, tmp_path, dialect):
+    stream = wire_edges.stream()
+    kinds = _against_the_definition(stream, _lines(program, dialect, stream, tmp_path), dialect)
+    compared = sum(map(len, kinds.values())) - len(kinds["skip"])
+    print(f"{dialect}: {compared} progress frames, {len(kinds['host'])} left to the host")
+    assert compared == len(wire_edges.bodies()) and len(kinds["event"]) > 2000 and len(kinds["error"]) > 2000
+    assert len(kinds["host"]) <= wire_edges.HOST_CAP[dialect] * compared
+    if dialect == "protobufjs":
+        assert kinds["host"] == _rule(stream)
 
 
 @pytest.mark.parametrize("dialect", ops.DIALECTS)

@@ -22,6 +22,7 @@ from beholder_amd.topics import PROGRESS_ID, STATUS_ID
 
 np = pytest.importorskip("numpy")
 from beholder_amd.ops import gpu_decode as gd  # noqa: E402
+import wire_edges  # noqa: E402
 from telemetry_corpus import decode_corpus, fold_corpus  # noqa: E402
 
 pytestmark = pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
@@ -64,15 +65,15 @@ def _high(b: bytes) -> bool:
     return any(c >= 0x80 for c in b)
 
 
-def _against_codec(stream: bytes, rows, dialect: str):
+def _against_codec(stream: bytes, rows, dialect: str, left: set = None):
     """Asserts the rows against the service's codec; returns (frames left out, compared frames the
-    codec raises on)."""
+    codec raises on). The indices of the frames left out are added to ``left`` where given."""
     index = _frames_12(stream)
     assert len(rows) == len(index)
     codecs = {t: ops.codec_for(p, dialect) for t, p in TYPES.items()}
     left_out = raised = 0
     bad = []
-    for (topic, start, end), row in zip(index, rows.tolist()):
+    for k, ((topic, start, end), row) in enumerate(zip(index, rows.tolist())):
         id_off, id_len, status, progress, host_off, host_len, ok, _ = row
         try:
             m = codecs[topic].decode(stream[start:end])
@@ -86,6 +87,8 @@ def _against_codec(stream: bytes, rows, dialect: str):
         upb_host = dialect == "upb" and topic == PROGRESS_ID
         if ok == OK_HOST or ok == OK_DECODED and (_high(mid) or upb_host and _high(host)):
             left_out += 1
+            if left is not None:
+                left.add(k)
             continue
         raised += want is None
         # protobufjs decodes invalid UTF-8 to U+FFFD; upb strings that reach this line are ASCII
@@ -139,3 +142,42 @@ def test_plain_upb_reads_both_message_types_in_bounds(program, tmp_path):
         else:
             assert row[3] == 0 and row[5] == 0 and not row[7] & 12, (stream[start:end], row)
             assert row[1] == 0 or start <= row[0] and row[0] + row[1] <= end, (stream[start:end], row)
+
+
+# ---- the systematic corpus (wire_edges.py) ------------------------------------------------------
+
+@pytest.mark.parametrize("dialect", ops.DIALECTS)
+def test_readers_agree_with_the_service_codec_on_the_wire_edges(program, tmp_path, dialect):
+    """Both message types in the codec's form of each dialect over every body of the corpus. upb's
+    STRICT reader hands the group families over by design; under protobufjs the frames left out are
+    exactly those that decode to an id that is not ASCII."""
+    stream = wire_edges.stream()
+    rows = _rows(program, MODES[dialect], stream, tmp_path)
+    left = set()
+    left_out, raised = _against_codec(stream, rows, dialect, left)
+    print(f"{dialect}: {len(rows)} topic-1/2 frames, {left_out} left to the host, the codec raises on {raised}")
+    assert len(rows) == 2 * len(wire_edges.bodies())
+    assert left_out <= wire_edges.HOST_CAP[dialect] * len(rows)
+    if dialect == "protobufjs":
+        want = wire_edges.expected(dialect)
+        assert left == {k for k, v in enumerate(want) if v is not None and not v.media_id.isascii()}
+
+
+def test_plain_upb_follows_its_definition_on_the_wire_edges(program, tmp_path):
+    """The decode kernel's plain upb reader against ``gpu_decode.reference_decode``, exactly, on every
+    body: as a progress the row itself, as a status the same walk with fields 3 and 4 unknown. A tag
+    whose field number is 2^32 + k is an unknown field, not field k."""
+    stream = wire_edges.stream()
+    rows = _rows(program, "upb", stream, tmp_path)
+    index = _frames_12(stream)
+    assert len(rows) == len(index)
+    bad = []
+    for (topic, start, end), row in zip(index, rows.tolist()):
+        want = gd.reference_decode(stream, start, end)
+        if topic == STATUS_ID:
+            want = want[:3] + [0, 0, 0, want[6], want[7] & 3]
+        if row != want:
+            bad.append((topic, stream[start:end], row, want))
+    assert not bad, (len(bad), bad[:5])
+    wide = [k for k, (_, start, end) in enumerate(index) if stream[start:end] == bytes.fromhex("8a808080800101 6d")]
+    assert len(wide) == 2 and all(rows[k].tolist() == [0, 0, 0, 0, 0, 0, OK_DECODED, 0] for k in wide)

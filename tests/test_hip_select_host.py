@@ -26,6 +26,7 @@ from beholder_amd.transport.framing import iter_frames
 
 np = pytest.importorskip("numpy")
 from beholder_amd.ops import gpu_extract as gx, gpu_fold  # noqa: E402
+import wire_edges  # noqa: E402
 from extract_cases import KINDS, collision_pairs  # noqa: E402
 from telemetry_corpus import body as _body, fold_corpus  # noqa: E402
 
@@ -101,6 +102,18 @@ def test_the_predicate_agrees_with_the_definition_on_the_fold_corpus(program, tm
     assert len(got) > 5000 and 0 < host <= 0.05 * len(got)  # the comparison covers what the device decides itself
     if kind not in ("all", "combined"):
         assert "keep" in got and "drop" in got
+
+
+@pytest.mark.parametrize("dialect", ops.DIALECTS)
+def test_the_predicate_agrees_with_the_definition_on_the_wire_edges(program, tmp_path, dialect):
+    """Under a selector that keeps by media and by status; ``_against_the_definition`` holds the host
+    set to the rule in both directions under protobufjs."""
+    stream, selector = wire_edges.stream(), wire_edges.selector()
+    got = _decisions(program, dialect, stream, selector, tmp_path)
+    host = _against_the_definition(stream, got, selector, dialect)
+    print(f"{dialect}: {len(got)} frames, {host} left to the host")
+    assert len(got) == 2 * len(wire_edges.bodies()) and got.count("keep") > 1000 and got.count("drop") > 1000
+    assert host <= wire_edges.HOST_CAP[dialect] * len(got)
 
 
 def test_the_host_set_does_not_depend_on_the_selector(program, tmp_path):

@@ -19,6 +19,7 @@ from beholder_amd.models import proto
 from beholder_amd.shard import DROP, Policy
 from beholder_amd.topics import PROGRESS_ID, STATUS_ID
 from beholder_amd.transport.framing import iter_frames
+import wire_edges
 from shard_cases import POLICIES, corpus, mixed_stream, policy_id
 
 pytestmark = pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
@@ -104,6 +105,19 @@ def test_the_decision_agrees_with_the_definition_on_the_fold_corpus(program, tmp
     numbers = {int(w) for w in kinds - {"drop", "host"}}
     assert numbers <= set(range(policy.shards))
     assert len(numbers) == policy.shards if policy.shards <= 7 else len(numbers) > 20  # some 70 ids
+
+
+@pytest.mark.parametrize("dialect", ops.DIALECTS)
+@pytest.mark.parametrize("policy", [Policy(7), Policy(256, "drop")], ids=policy_id)
+def test_the_decision_agrees_with_the_definition_on_the_wire_edges(program, tmp_path, policy, dialect):
+    stream = wire_edges.stream()
+    got = _decisions(program, dialect, stream, policy, tmp_path)
+    host = _against_the_definition(stream, got, policy, dialect)
+    print(f"{dialect}: {len(got)} frames, {len(host)} left to the host")
+    assert len(got) == 2 * len(wire_edges.bodies()) and len(set(got)) > 4  # the ids are few
+    assert len(host) <= wire_edges.HOST_CAP[dialect] * len(got)
+    if dialect == "protobufjs":
+        assert host == _rule(list(wire_edges.events()), dialect)
 
 
 @pytest.mark.parametrize("dialect", ops.DIALECTS)

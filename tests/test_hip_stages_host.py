@@ -23,6 +23,7 @@ from beholder_amd.transport.framing import iter_frames
 
 np = pytest.importorskip("numpy")  # gpu_fold imports it
 from beholder_amd.ops import gpu_fold  # noqa: E402
+import wire_edges  # noqa: E402
 from stages_cases import bucket_edges, corpus, non_ascii_stream, random_stream, stitch_stream  # noqa: E402
 from telemetry_corpus import MALFORMED_FOLD, malformed  # noqa: E402
 from thin_cases import PERCENTAGES, mixed_stream  # noqa: E402
@@ -115,6 +116,19 @@ def test_the_lines_agree_with_the_definition_on_the_fold_corpus(program, tmp_pat
     total = sum(map(len, kinds.values()))
     assert total == 5711 and len(kinds["host"]) <= 0.05 * total  # the comparison covers what the device decides
     assert kinds["skip"] == {i for i, (topic, _) in enumerate(iter_frames(stream)) if topic not in TYPES}
+    if dialect == "protobufjs":
+        assert kinds["host"] == _rule(stream)
+
+
+@pytest.mark.parametrize("dialect", ops.DIALECTS)
+def test_the_lines_agree_with_the_definition_on_the_wire_edges(program, tmp_path, dialect):
+    stream = wire_edges.stream()
+    kinds = _against_the_definition(stream, _lines(program, dialect, stream, tmp_path), dialect)
+    compared = sum(map(len, kinds.values()))
+    print(f"{dialect}: {compared} frames, {len(kinds['host'])} left to the host")
+    assert compared == 2 * len(wire_edges.bodies()) and not kinds["skip"] and len(kinds["error"]) > 4000
+    assert len(kinds["status"]) > 2000 and len(kinds["progress"]) > 2000
+    assert len(kinds["host"]) <= wire_edges.HOST_CAP[dialect] * compared
     if dialect == "protobufjs":
         assert kinds["host"] == _rule(stream)
 
