@@ -11,6 +11,7 @@ transitions  count a framed stream's per-media status moves: the transition matr
 hosts    what every worker host did in a framed stream: events, media, stints, handovers, what it held (``hosts``).
 stages   join both topics of a framed stream per media: what stage each is in and how far (``stages``).
 extract  cut a framed stream down to selected frames, a framed stream again (``extract``).
+normalise  rewrite every decodable event of a framed stream in its canonical encoding, a framed stream again (``normalise``).
 dedupe   drop the byte-identical repeat frames of a framed stream, a framed stream again (``dedupe``).
 thin     drop the progress events that repeat their media's step, a framed stream again (``thin``).
 coalesce  cut a framed stream down to the frames that set its end state, a framed stream again (``coalesce``).
@@ -574,6 +575,47 @@ def cmd_thin(a: argparse.Namespace) -> int:
     return 0
 
 
+def cmd_normalise(a: argparse.Namespace) -> int:
+    """Rewrite every decodable event of a framed stream in canonical form (``beholder_amd.normalise``)."""
+    from . import normalise
+    policy = normalise.Policy(undecoded=a.undecoded)  # argparse checked the value
+    if a.device == "gpu":
+        try:
+            import torch
+
+            from .ops import gpu_normalise, hip_lib  # noqa: F401  gpu_normalise: its imports fail here, not mid-run
+            if not torch.cuda.is_available():
+                raise RuntimeError("no GPU is visible")
+            hip_lib.lib()
+        except (ImportError, RuntimeError, OSError) as e:
+            print(f"beholder: --device gpu is not available ({e}); use --device cpu", file=sys.stderr)
+            return 1
+    source = a.input if a.input else sys.stdin.buffer
+    out = _LazyOutput(a.out)
+    indices = _LazyOutput(a.indices, text=True) if a.indices else None
+    failed = None
+    try:
+        counts = normalise.normalise_file(source, out, policy, device=a.device, dialect=a.dialect,
+                                          chunk_bytes=a.chunk_bytes, indices_out=indices)
+    except ValueError as e:  # broken framing, or a chunk too large for the device: whole frames only were written
+        failed = e
+    for f in (out, indices):
+        if f is None:
+            continue
+        if failed is None:
+            f.finish()
+        elif f.file is not None:
+            if f.name == "-" and not f.text:
+                f.file.flush()
+            else:
+                f.file.close()
+    if failed is not None:
+        print(f"beholder: {failed}", file=sys.stderr)
+        return 1
+    print(json.dumps(counts), file=sys.stderr)
+    return 0
+
+
 def cmd_shard(a: argparse.Namespace) -> int:
     """Split a framed stream by media into N framed streams (``beholder_amd.shard``)."""
     from . import shard
@@ -818,6 +860,22 @@ def build_parser() -> argparse.ArgumentParser:
     o.add_argument("--chunk-bytes", type=int, default=256 << 20, help="cut the input in pieces of this size")
     o.add_argument("--indices", metavar="FILE", help="write the kept frames' input indices here, one per line")
     o.set_defaults(fn=cmd_coalesce)
+
+    z = sub.add_parser("normalise", help="framed stream -> the same with every event in its canonical encoding",
+                       description="Decode every status and progress frame in the dialect it was captured under "
+                                   "and write it as the service's own encoder would: fields in order, defaults "
+                                   "omitted, unknown fields gone. Run it first, before dedupe. "
+                                   "The counts go to stderr as one JSON line.")
+    z.add_argument("input", nargs="?")
+    z.add_argument("-o", "--out", default="-", help="output file (default '-': stdout)")
+    z.add_argument("--undecoded", choices=["keep", "drop"], default="keep",
+                   help="frames that fail to decode or carry another topic byte: as they are, or nowhere")
+    z.add_argument("--device", choices=["cpu", "gpu"], default="cpu",
+                   help="cpu: the definition, runs anywhere; gpu: the gfx950 normalise kernels")
+    z.add_argument("--dialect", choices=["protobufjs", "upb"], default="protobufjs")
+    z.add_argument("--chunk-bytes", type=int, default=256 << 20, help="cut the input in pieces of this size")
+    z.add_argument("--indices", metavar="FILE", help="write the output frames' input indices here, one per line")
+    z.set_defaults(fn=cmd_normalise)
 
     h = sub.add_parser("shard", help="framed stream -> N framed streams, split by media, for parallel replay in order",
                        description="Every mediaId's events go to one shard, in their original order; the shard "

@@ -11,7 +11,8 @@ repeats, and is the definition; :func:`dedupe_gpu` computes the same :class:`Ded
 
 A frame's **content** is its topic byte and body: the bytes after the length header. Two frames are
 equal iff their contents are equal bytes. Nothing is decoded, so there is no dialect, and two
-encodings of one event are two contents. Under ``keep="last"`` **a frame is kept iff no later frame
+encodings of one event are two contents (:mod:`beholder_amd.normalise`, run first, gives every event
+one encoding). Under ``keep="last"`` **a frame is kept iff no later frame
 has its content**; under ``keep="first"`` iff no earlier one has. With ``topics`` only frames of
 those topic bytes take part; every other frame is kept as it is and equals nothing.
 

@@ -2,7 +2,7 @@
 loaded, and what its callers share: the launch helper, the argument checks and the reader of the
 overflow list (``ops/gpu_decode.py``, ``ops/gpu_fold.py``, ``ops/gpu_extract.py``,
 ``ops/gpu_coalesce.py``, ``ops/gpu_shard.py``, ``ops/gpu_dedupe.py``, ``ops/gpu_transitions.py``,
-``ops/gpu_thin.py``, ``ops/gpu_hosts.py``, ``ops/gpu_stages.py``).
+``ops/gpu_thin.py``, ``ops/gpu_hosts.py``, ``ops/gpu_stages.py``, ``ops/gpu_normalise.py``).
 
 The library is built in-tree by ``beholder_amd._build.build_hip`` (hipcc, gfx950) and loaded with
 ctypes after ``import torch``. torch's HIP runtime has the same soname, so the kernels launch on
@@ -84,6 +84,11 @@ def lib() -> ctypes.CDLL:
         so.bh_stages_carry.restype = i
         so.bh_stages_settle.argtypes = [p] * 6 + [i, i, ctypes.c_ulonglong] + [p] * 4
         so.bh_stages_settle.restype = i
+        # telemetry_normalise.hip (ops/gpu_normalise.py): classify, emit
+        so.bh_normalise_classify.argtypes = [p, p, i, i, i] + [p] * 5
+        so.bh_normalise_classify.restype = i
+        so.bh_normalise_emit.argtypes = [p, p, i] + [p] * 5
+        so.bh_normalise_emit.restype = i
         _lib = so
     return _lib
 
