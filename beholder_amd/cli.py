@@ -16,12 +16,13 @@ dedupe   drop the byte-identical repeat frames of a framed stream, a framed stre
 thin     drop the progress events that repeat their media's step, a framed stream again (``thin``).
 coalesce  cut a framed stream down to the frames that set its end state, a framed stream again (``coalesce``).
 shard    split a framed stream by media into N framed streams, each media's events in order (``shard``).
+compare  match two framed streams frame for frame: what is only in one, what is in both, in what order (``compare``).
 seed     load a media fixture into a sqlite/postgres store.
 bench    run the BASELINE.json measurement configs (see ``beholder_amd.bench.harness``).
 publish  publish a framed stream to an AMQP broker.
 
 Exit codes: 0 ok, 1 runtime failure, 2 usage/config error (startup failures are
-fatal — the documented fix of quirk Q10).
+fatal — the documented fix of quirk Q10); ``compare --exit-code`` adds 3, the captures differ.
 """
 from __future__ import annotations
 
@@ -530,6 +531,40 @@ def cmd_dedupe(a: argparse.Namespace) -> int:
     return 0
 
 
+def cmd_compare(a: argparse.Namespace) -> int:
+    """Match two framed streams frame for frame (``beholder_amd.compare``)."""
+    from . import compare
+    try:
+        policy = compare.Policy(topics={_topic_byte(t) for t in a.topic} if a.topic else None)
+    except ValueError as e:
+        print(f"beholder: {e}", file=sys.stderr)
+        return 2
+    if a.device == "gpu":
+        try:
+            import torch
+
+            from .ops import gpu_compare, hip_lib  # noqa: F401  gpu_compare: its imports fail here, not mid-run
+            if not torch.cuda.is_available():
+                raise RuntimeError("no GPU is visible")
+            hip_lib.lib()
+        except (ImportError, RuntimeError, OSError) as e:
+            print(f"beholder: --device gpu is not available ({e}); use --device cpu", file=sys.stderr)
+            return 1
+    outs = [_LazyOutput(name, text=text) if name else None
+            for name, text in ((a.only_a, False), (a.only_b, False), (a.indices_a, True), (a.indices_b, True))]
+    try:
+        counts = compare.compare_file(a.a, a.b, outs[0], outs[1], policy, device=a.device,
+                                      indices_a_out=outs[2], indices_b_out=outs[3])
+    except (ValueError, OSError) as e:  # broken framing, captures beyond the device's limit: nothing was written
+        print(f"beholder: {e}", file=sys.stderr)
+        return 1
+    for f in outs:
+        if f is not None:
+            f.finish()
+    print(json.dumps(counts))
+    return 3 if a.exit_code and not counts["equal"] else 0
+
+
 def cmd_thin(a: argparse.Namespace) -> int:
     """Drop the progress events that repeat their media's step (``beholder_amd.thin``)."""
     from . import thin
@@ -894,6 +929,25 @@ def build_parser() -> argparse.ArgumentParser:
     h.add_argument("--indices", metavar="PATTERN",
                    help="write each shard's input indices to these files, one per line; '{}' as in -o")
     h.set_defaults(fn=cmd_shard)
+
+    m = sub.add_parser("compare", help="two framed streams -> what is only in one, what is in both, in what order",
+                       description="Match A and B as multisets of frames: the k-th occurrence of a content (topic "
+                                   "byte and body) in A is paired with the k-th in B, every other frame is only "
+                                   "in its capture. Nothing is decoded; run normalise on both first if two "
+                                   "encodings of one event should count as equal. The counts go to stdout as "
+                                   "one JSON object.")
+    m.add_argument("a", metavar="A")
+    m.add_argument("b", metavar="B")
+    m.add_argument("--topic", action="append", metavar="status|progress|N",
+                   help="only frames of this topic byte take part, the others are skipped; repeatable")
+    m.add_argument("--only-a", metavar="PATH", help="write the frames only in A here, a framed stream")
+    m.add_argument("--only-b", metavar="PATH", help="write the frames only in B here, a framed stream")
+    m.add_argument("--indices-a", metavar="PATH", help="write the indices in A of the frames only in A, one per line")
+    m.add_argument("--indices-b", metavar="PATH", help="write the indices in B of the frames only in B, one per line")
+    m.add_argument("--device", choices=["cpu", "gpu"], default="cpu",
+                   help="cpu: the definition, runs anywhere; gpu: the gfx950 compare kernels")
+    m.add_argument("--exit-code", action="store_true", help="exit with status 3 where the captures differ")
+    m.set_defaults(fn=cmd_compare)
 
     s = sub.add_parser("seed", help="load a media fixture into a store")
     s.add_argument("fixture")

@@ -23,8 +23,10 @@ coalesce key is the last occurrence of its own content, so it survives ``last``:
 deduped stream gives what coalescing the input gives, and the fold ends on the same statuses.
 
 Content cannot tell "the same event again" from "the same state reached again": two reports of one
-progress percentage are equal frames and collapse too. That is why subtracting one capture from
-another is not offered.
+progress percentage are equal frames and collapse too. That is why one capture is never subtracted
+from another as a *set*: one such frame in B would erase both of A's. What is offered is the multiset
+comparison of :mod:`beholder_amd.compare`, which pairs the k-th occurrence of a content in A with
+the k-th in B, so two in A and one in B leave one "only in A", and which claims nothing about why.
 
 Results merge: ``dedupe(a + b) == dedupe(a).merge(dedupe(b))`` for a cut at any frame boundary,
 which is how :func:`dedupe_file` handles a file of any size in chunks. And deduping is idempotent.

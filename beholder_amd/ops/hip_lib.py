@@ -2,7 +2,8 @@
 loaded, and what its callers share: the launch helper, the argument checks and the reader of the
 overflow list (``ops/gpu_decode.py``, ``ops/gpu_fold.py``, ``ops/gpu_extract.py``,
 ``ops/gpu_coalesce.py``, ``ops/gpu_shard.py``, ``ops/gpu_dedupe.py``, ``ops/gpu_transitions.py``,
-``ops/gpu_thin.py``, ``ops/gpu_hosts.py``, ``ops/gpu_stages.py``, ``ops/gpu_normalise.py``).
+``ops/gpu_thin.py``, ``ops/gpu_hosts.py``, ``ops/gpu_stages.py``, ``ops/gpu_normalise.py``,
+``ops/gpu_compare.py``).
 
 The library is built in-tree by ``beholder_amd._build.build_hip`` (hipcc, gfx950) and loaded with
 ctypes after ``import torch``. torch's HIP runtime has the same soname, so the kernels launch on
@@ -89,6 +90,15 @@ def lib() -> ctypes.CDLL:
         so.bh_normalise_classify.restype = i
         so.bh_normalise_emit.argtypes = [p, p, i] + [p] * 5
         so.bh_normalise_emit.restype = i
+        # telemetry_compare.hip (ops/gpu_compare.py): classify, bounds, match, breaks
+        so.bh_compare_classify.argtypes = [p, p, i, i] + [p] * 9
+        so.bh_compare_classify.restype = i
+        so.bh_compare_bounds.argtypes = [p, p, i, i] + [p] * 4
+        so.bh_compare_bounds.restype = i
+        so.bh_compare_match.argtypes = [p, p, i, i, p, i] + [p] * 9
+        so.bh_compare_match.restype = i
+        so.bh_compare_breaks.argtypes = [p, i, p, i, p, p]
+        so.bh_compare_breaks.restype = i
         _lib = so
     return _lib
 
