@@ -6,6 +6,7 @@ run      start the service (``--source amqp|stdin|file``); the reference's only 
 config   validate and print the effective config (secrets masked).
 gen      write synthetic framed telemetry to stdout/a file (+ optional media fixture).
 decode   turn a framed stream into NDJSON (debugging).
+export   write a framed stream as NDJSON rows, one per frame with its index, read in the service's dialect (``export``).
 summarise  fold a framed stream into its end state: counters, comments, final statuses (``replay``).
 transitions  count a framed stream's per-media status moves: the transition matrix, changes, repeats (``transitions``).
 hosts    what every worker host did in a framed stream: events, media, stints, handovers, what it held (``hosts``).
@@ -651,6 +652,47 @@ def cmd_normalise(a: argparse.Namespace) -> int:
     return 0
 
 
+def cmd_export(a: argparse.Namespace) -> int:
+    """Write a framed stream as NDJSON rows, one per frame (``beholder_amd.export``)."""
+    from . import export
+    policy = export.Policy(undecoded=a.undecoded)  # argparse checked the value
+    if a.device == "gpu":
+        try:
+            import torch
+
+            from .ops import gpu_export, hip_lib  # noqa: F401  gpu_export: its imports fail here, not mid-run
+            if not torch.cuda.is_available():
+                raise RuntimeError("no GPU is visible")
+            hip_lib.lib()
+        except (ImportError, RuntimeError, OSError) as e:
+            print(f"beholder: --device gpu is not available ({e}); use --device cpu", file=sys.stderr)
+            return 1
+    source = a.input if a.input else sys.stdin.buffer
+    out = _LazyOutput(a.out)
+    indices = _LazyOutput(a.indices, text=True) if a.indices else None
+    failed = None
+    try:
+        counts = export.export_file(source, out, policy, device=a.device, dialect=a.dialect, chunk_bytes=a.chunk_bytes,
+                                    indices_out=indices)
+    except ValueError as e:  # broken framing, or a chunk too large for the device: whole rows only were written
+        failed = e
+    for f in (out, indices):
+        if f is None:
+            continue
+        if failed is None:
+            f.finish()
+        elif f.file is not None:
+            if f.name == "-" and not f.text:
+                f.file.flush()
+            else:
+                f.file.close()
+    if failed is not None:
+        print(f"beholder: {failed}", file=sys.stderr)
+        return 1
+    print(json.dumps(counts), file=sys.stderr)
+    return 0
+
+
 def cmd_shard(a: argparse.Namespace) -> int:
     """Split a framed stream by media into N framed streams (``beholder_amd.shard``)."""
     from . import shard
@@ -911,6 +953,24 @@ def build_parser() -> argparse.ArgumentParser:
     z.add_argument("--chunk-bytes", type=int, default=256 << 20, help="cut the input in pieces of this size")
     z.add_argument("--indices", metavar="FILE", help="write the output frames' input indices here, one per line")
     z.set_defaults(fn=cmd_normalise)
+
+    x = sub.add_parser("export", help="framed stream -> NDJSON rows, one per frame, for jq, DuckDB, pandas and grep",
+                       description="Decode every status and progress frame in the dialect it was captured under "
+                                   "and write one JSON row per frame: its index in the input, its topic, and "
+                                   "its fields with the status name, or the body as base64 where it does not "
+                                   "decode. The rows are NDJSON input to the service again. "
+                                   "The counts go to stderr as one JSON line.")
+    x.add_argument("input", nargs="?")
+    x.add_argument("-o", "--out", default="-", help="output file (default '-': stdout)")
+    x.add_argument("--undecoded", choices=["keep", "drop"], default="keep",
+                   help="frames that fail to decode or carry another topic byte: a base64 row, or none")
+    x.add_argument("--device", choices=["cpu", "gpu"], default="cpu",
+                   help="cpu: the definition, runs anywhere; gpu: the gfx950 export kernels")
+    x.add_argument("--dialect", choices=["protobufjs", "upb"], default="protobufjs")
+    x.add_argument("--chunk-bytes", type=int, default=64 << 20,
+                   help="cut the input in pieces of this size (the rows take several times the input's bytes)")
+    x.add_argument("--indices", metavar="FILE", help="write the rows' frame indices here, one per line")
+    x.set_defaults(fn=cmd_export)
 
     h = sub.add_parser("shard", help="framed stream -> N framed streams, split by media, for parallel replay in order",
                        description="Every mediaId's events go to one shard, in their original order; the shard "
