@@ -13,6 +13,7 @@ hosts    what every worker host did in a framed stream: events, media, stints, h
 stages   join both topics of a framed stream per media: what stage each is in and how far (``stages``).
 extract  cut a framed stream down to selected frames, a framed stream again (``extract``).
 normalise  rewrite every decodable event of a framed stream in its canonical encoding, a framed stream again (``normalise``).
+anonymise  replace every mediaId and host of a framed stream by a keyed pseudonym, a framed stream again (``anonymise``).
 dedupe   drop the byte-identical repeat frames of a framed stream, a framed stream again (``dedupe``).
 thin     drop the progress events that repeat their media's step, a framed stream again (``thin``).
 coalesce  cut a framed stream down to the frames that set its end state, a framed stream again (``coalesce``).
@@ -652,6 +653,98 @@ def cmd_normalise(a: argparse.Namespace) -> int:
     return 0
 
 
+ANONYMISE_KEY_ENV = "BEHOLDER_ANONYMISE_KEY"
+
+
+def _anonymise_key(a: argparse.Namespace) -> bytes:
+    """The key from exactly one source; ``ValueError`` for none, several or a bad value. There is no
+    option that takes the key itself: it would show in ``ps``."""
+    env = os.environ.get(ANONYMISE_KEY_ENV)
+    sources = [name for name, given in (("--key-file", a.key_file is not None), (f"${ANONYMISE_KEY_ENV}", bool(env)),
+                                        ("--random-key", a.random_key)) if given]
+    if len(sources) != 1:
+        raise ValueError("the key comes from exactly one of --key-file, $%s and --random-key (%s)"
+                         % (ANONYMISE_KEY_ENV, "given: " + ", ".join(sources) if sources else "none given"))
+    if a.key_file is not None:
+        try:
+            with open(a.key_file, "rb") as f:
+                key = f.read(65)  # as it is: no stripping
+        except OSError as e:
+            raise ValueError(f"--key-file: {e}") from None
+    elif a.random_key:
+        key = os.urandom(32)  # never shown, never stored
+    else:
+        try:
+            key = bytes.fromhex(env)
+        except ValueError:
+            raise ValueError(f"${ANONYMISE_KEY_ENV} is hex") from None
+    if not 16 <= len(key) <= 32:
+        raise ValueError(f"the key from {sources[0]} has {len(key) if len(key) < 65 else 'more than 64'} bytes: "
+                         "16 to 32 are needed")
+    return key
+
+
+def cmd_anonymise(a: argparse.Namespace) -> int:
+    """Replace every mediaId and host of a framed stream by a keyed pseudonym (``beholder_amd.anonymise``)."""
+    from . import anonymise
+    try:
+        if a.keep_media and a.keep_host:
+            raise ValueError("--keep-media and --keep-host together leave nothing to replace")
+        requests = []
+        for request in a.pseudonym_of or []:
+            field, eq, value = request.partition("=")
+            if not eq or field not in anonymise.PERSON:
+                raise ValueError(f"--pseudonym-of takes mediaId=VALUE or host=VALUE, not {request!r}")
+            requests.append((field, value))
+        fields = anonymise.FIELDS - ({"mediaId"} if a.keep_media else set()) - ({"host"} if a.keep_host else set())
+        policy = anonymise.Policy(_anonymise_key(a), undecoded=a.undecoded, fields=frozenset(fields))
+    except ValueError as e:
+        print(f"beholder: {e}", file=sys.stderr)
+        return 2
+    if requests:  # the key's owner translates a finding back; no capture is read
+        for field, value in requests:
+            print(f"{field}\t{value}\t{anonymise.pseudonym_of(policy.key, field, value)}")
+        return 0
+    if a.device == "gpu":
+        try:
+            import torch
+
+            from .ops import gpu_anonymise, hip_lib  # noqa: F401  gpu_anonymise: its imports fail here, not mid-run
+            if not torch.cuda.is_available():
+                raise RuntimeError("no GPU is visible")
+            hip_lib.lib()
+        except (ImportError, RuntimeError, OSError) as e:
+            print(f"beholder: --device gpu is not available ({e}); use --device cpu", file=sys.stderr)
+            return 1
+    source = a.input if a.input else sys.stdin.buffer
+    out = _LazyOutput(a.out)
+    indices = _LazyOutput(a.indices, text=True) if a.indices else None
+    failed = None
+    try:
+        counts = anonymise.anonymise_file(source, out, policy, device=a.device, dialect=a.dialect,
+                                          chunk_bytes=a.chunk_bytes, indices_out=indices)
+    except ValueError as e:  # broken framing, or a chunk too large for the device: whole frames only were written
+        failed = e
+    for f in (out, indices):
+        if f is None:
+            continue
+        if failed is None:
+            f.finish()
+        elif f.file is not None:
+            if f.name == "-" and not f.text:
+                f.file.flush()
+            else:
+                f.file.close()
+    if failed is not None:
+        print(f"beholder: {failed}", file=sys.stderr)
+        return 1
+    if policy.undecoded == "keep" and counts["undecoded"]:
+        print(f"beholder: warning: {counts['undecoded']} undecoded frames were kept byte for byte; they may hold "
+              "names in clear", file=sys.stderr)
+    print(json.dumps(counts), file=sys.stderr)
+    return 0
+
+
 def cmd_export(a: argparse.Namespace) -> int:
     """Write a framed stream as NDJSON rows, one per frame (``beholder_amd.export``)."""
     from . import export
@@ -953,6 +1046,32 @@ def build_parser() -> argparse.ArgumentParser:
     z.add_argument("--chunk-bytes", type=int, default=256 << 20, help="cut the input in pieces of this size")
     z.add_argument("--indices", metavar="FILE", help="write the output frames' input indices here, one per line")
     z.set_defaults(fn=cmd_normalise)
+
+    y = sub.add_parser("anonymise", help="framed stream -> the same with every mediaId and host a keyed pseudonym",
+                       description="Write every decoded status and progress event in its canonical encoding with "
+                                   "mediaId and host replaced by keyed pseudonyms (BLAKE2s, 32 hex characters): "
+                                   "the same key gives the same pseudonym in every run and capture, so the "
+                                   "reports of the output are the input's up to renaming. The key comes from "
+                                   "--key-file, $BEHOLDER_ANONYMISE_KEY (hex) or --random-key, exactly one. "
+                                   "The counts go to stderr as one JSON line.")
+    y.add_argument("input", nargs="?")
+    y.add_argument("-o", "--out", default="-", help="output file (default '-': stdout)")
+    y.add_argument("--key-file", metavar="PATH", help="the key: this file's bytes as they are, 16 to 32")
+    y.add_argument("--random-key", action="store_true",
+                   help="a fresh key that is never shown or stored: consistent output, linkable to nothing else")
+    y.add_argument("--undecoded", choices=["drop", "keep"], default="drop",
+                   help="frames that fail to decode or carry another topic byte: nowhere, or as they are, with "
+                        "whatever names they hold")
+    y.add_argument("--keep-media", action="store_true", help="leave mediaId in clear")
+    y.add_argument("--keep-host", action="store_true", help="leave host in clear")
+    y.add_argument("--pseudonym-of", action="append", metavar="mediaId=VALUE|host=VALUE",
+                   help="print field, value and pseudonym, tab-separated, and read no capture; repeatable")
+    y.add_argument("--device", choices=["cpu", "gpu"], default="cpu",
+                   help="cpu: the definition, runs anywhere; gpu: the gfx950 anonymise kernels")
+    y.add_argument("--dialect", choices=["protobufjs", "upb"], default="protobufjs")
+    y.add_argument("--chunk-bytes", type=int, default=256 << 20, help="cut the input in pieces of this size")
+    y.add_argument("--indices", metavar="FILE", help="write the output frames' input indices here, one per line")
+    y.set_defaults(fn=cmd_anonymise)
 
     x = sub.add_parser("export", help="framed stream -> NDJSON rows, one per frame, for jq, DuckDB, pandas and grep",
                        description="Decode every status and progress frame in the dialect it was captured under "

@@ -111,6 +111,14 @@ def decide_on_host(t: Tables, data, offs: np.ndarray, policy, dialect: str = "pr
     """Reads the overflow list's length; where it is not 0, asks ``normalise.canon_of`` about those
     frames and writes the lengths of their output frames into ``t.keep_len``. Raises
     :class:`TooLarge` where they grow the output past what the scan's 32 bits hold."""
+    from .. import normalise
+    return decide_with(t, data, offs, lambda: normalise.canon_of(policy, dialect), check_size)
+
+
+def decide_with(t, data, offs: np.ndarray, make_canon, check) -> HostFrames:
+    """:func:`decide_on_host` for any tables of this shape (``ops/gpu_anonymise.py`` has its own):
+    ``make_canon()`` gives the per-frame function, made only where the list is not empty, and
+    ``check(size, n, extra)`` is the caller's size check."""
     import torch
 
     from .. import normalise
@@ -118,7 +126,7 @@ def decide_on_host(t: Tables, data, offs: np.ndarray, policy, dialect: str = "pr
     count = int(t.counters[C_OVERFLOW].item())
     if count == 0:
         return NO_HOST_FRAMES
-    canon = normalise.canon_of(policy, dialect)
+    canon = make_canon()
     where, parts = [], []
     events = rewritten = growth = 0
     for i, topic, body in hip_lib.overflow_frames(t.overflow, count, data, offs)[1]:
@@ -133,7 +141,7 @@ def decide_on_host(t: Tables, data, offs: np.ndarray, policy, dialect: str = "pr
         growth += max(0, len(frame) - (int(offs[i + 1]) - int(offs[i])))
         where.append(i)
         parts.append(frame)
-    check_size(t.buf.numel(), t.n, growth)
+    check(t.buf.numel(), t.n, growth)
     frames = np.asarray(where, dtype=np.int64)
     if where:
         dev = t.buf.device

@@ -3,7 +3,7 @@ loaded, and what its callers share: the launch helper, the argument checks and t
 overflow list (``ops/gpu_decode.py``, ``ops/gpu_fold.py``, ``ops/gpu_extract.py``,
 ``ops/gpu_coalesce.py``, ``ops/gpu_shard.py``, ``ops/gpu_dedupe.py``, ``ops/gpu_transitions.py``,
 ``ops/gpu_thin.py``, ``ops/gpu_hosts.py``, ``ops/gpu_stages.py``, ``ops/gpu_normalise.py``,
-``ops/gpu_compare.py``, ``ops/gpu_export.py``).
+``ops/gpu_compare.py``, ``ops/gpu_export.py``, ``ops/gpu_anonymise.py``).
 
 The library is built in-tree by ``beholder_amd._build.build_hip`` (hipcc, gfx950) and loaded with
 ctypes after ``import torch``. torch's HIP runtime has the same soname, so the kernels launch on
@@ -104,6 +104,11 @@ def lib() -> ctypes.CDLL:
         so.bh_export_classify.restype = i
         so.bh_export_emit.argtypes = [p, i, ctypes.c_longlong] + [p] * 4
         so.bh_export_emit.restype = i
+        # telemetry_anonymise.hip (ops/gpu_anonymise.py): classify (the key is host memory), emit
+        so.bh_anonymise_classify.argtypes = [p, p, i, i, i, i, ctypes.c_char_p, i] + [p] * 5
+        so.bh_anonymise_classify.restype = i
+        so.bh_anonymise_emit.argtypes = [p, i] + [p] * 4
+        so.bh_anonymise_emit.restype = i
         _lib = so
     return _lib
 
