@@ -7,6 +7,7 @@ config   validate and print the effective config (secrets masked).
 gen      write synthetic framed telemetry to stdout/a file (+ optional media fixture).
 decode   turn a framed stream into NDJSON (debugging).
 export   write a framed stream as NDJSON rows, one per frame with its index, read in the service's dialect (``export``).
+import   read NDJSON rows back into a framed stream: the inverse of ``export`` (``import_rows``).
 summarise  fold a framed stream into its end state: counters, comments, final statuses (``replay``).
 transitions  count a framed stream's per-media status moves: the transition matrix, changes, repeats (``transitions``).
 hosts    what every worker host did in a framed stream: events, media, stints, handovers, what it held (``hosts``).
@@ -786,6 +787,46 @@ def cmd_export(a: argparse.Namespace) -> int:
     return 0
 
 
+def cmd_import(a: argparse.Namespace) -> int:
+    """Read NDJSON rows back into a framed stream (``beholder_amd.import_rows``)."""
+    from . import import_rows
+    policy = import_rows.Policy(malformed=a.malformed)  # argparse checked the value
+    if a.device == "gpu":
+        try:
+            import torch
+
+            from .ops import gpu_import, hip_lib  # noqa: F401  gpu_import: its imports fail here, not mid-run
+            if not torch.cuda.is_available():
+                raise RuntimeError("no GPU is visible")
+            hip_lib.lib()
+        except (ImportError, RuntimeError, OSError) as e:
+            print(f"beholder: --device gpu is not available ({e}); use --device cpu", file=sys.stderr)
+            return 1
+    source = a.input if a.input else sys.stdin.buffer
+    out = _LazyOutput(a.out)
+    lines = _LazyOutput(a.lines, text=True) if a.lines else None
+    failed = None
+    try:
+        counts = import_rows.import_file(source, out, policy, device=a.device, chunk_bytes=a.chunk_bytes, lines_out=lines)
+    except ValueError as e:  # a malformed row, or a chunk too large for the device: whole frames only were written
+        failed = e
+    for f in (out, lines):
+        if f is None:
+            continue
+        if failed is None:
+            f.finish()
+        elif f.file is not None:
+            if f.name == "-" and not f.text:
+                f.file.flush()
+            else:
+                f.file.close()
+    if failed is not None:
+        print(f"beholder: {failed}", file=sys.stderr)
+        return 1
+    print(json.dumps(counts), file=sys.stderr)
+    return 0
+
+
 def cmd_shard(a: argparse.Namespace) -> int:
     """Split a framed stream by media into N framed streams (``beholder_amd.shard``)."""
     from . import shard
@@ -1090,6 +1131,23 @@ def build_parser() -> argparse.ArgumentParser:
                    help="cut the input in pieces of this size (the rows take several times the input's bytes)")
     x.add_argument("--indices", metavar="FILE", help="write the rows' frame indices here, one per line")
     x.set_defaults(fn=cmd_export)
+
+    im = sub.add_parser("import", help="NDJSON rows -> framed stream: the inverse of export",
+                        description="Read one JSON row per line (topic with b64, or topic with json, as export "
+                                    "writes them) and write one frame per row: the base64 body verbatim, or the "
+                                    "fields in the canonical encoding. import of an export is the capture's "
+                                    "normalise. Blank lines are passed over. "
+                                    "The counts go to stderr as one JSON line.")
+    im.add_argument("input", nargs="?")
+    im.add_argument("-o", "--out", default="-", help="output file (default '-': stdout)")
+    im.add_argument("--malformed", choices=["fail", "skip"], default="fail",
+                   help="a line that is no row: stop there with its line number and exit 1, or leave it out and count it")
+    im.add_argument("--device", choices=["cpu", "gpu"], default="cpu",
+                   help="cpu: the definition, runs anywhere; gpu: the gfx950 import kernels")
+    im.add_argument("--chunk-bytes", type=int, default=256 << 20,
+                   help="cut the input after the last newline within this size")
+    im.add_argument("--lines", metavar="FILE", help="write the line numbers of the rows that became frames here, one per line")
+    im.set_defaults(fn=cmd_import)
 
     h = sub.add_parser("shard", help="framed stream -> N framed streams, split by media, for parallel replay in order",
                        description="Every mediaId's events go to one shard, in their original order; the shard "

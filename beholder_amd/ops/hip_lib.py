@@ -3,7 +3,7 @@ loaded, and what its callers share: the launch helper, the argument checks and t
 overflow list (``ops/gpu_decode.py``, ``ops/gpu_fold.py``, ``ops/gpu_extract.py``,
 ``ops/gpu_coalesce.py``, ``ops/gpu_shard.py``, ``ops/gpu_dedupe.py``, ``ops/gpu_transitions.py``,
 ``ops/gpu_thin.py``, ``ops/gpu_hosts.py``, ``ops/gpu_stages.py``, ``ops/gpu_normalise.py``,
-``ops/gpu_compare.py``, ``ops/gpu_export.py``, ``ops/gpu_anonymise.py``).
+``ops/gpu_compare.py``, ``ops/gpu_export.py``, ``ops/gpu_anonymise.py``, ``ops/gpu_import.py``).
 
 The library is built in-tree by ``beholder_amd._build.build_hip`` (hipcc, gfx950) and loaded with
 ctypes after ``import torch``. torch's HIP runtime has the same soname, so the kernels launch on
@@ -109,6 +109,15 @@ def lib() -> ctypes.CDLL:
         so.bh_anonymise_classify.restype = i
         so.bh_anonymise_emit.argtypes = [p, i] + [p] * 4
         so.bh_anonymise_emit.restype = i
+        # telemetry_import.hip (ops/gpu_import.py): count, starts, classify, emit
+        so.bh_import_count.argtypes = [p, ctypes.c_longlong, p, p]
+        so.bh_import_count.restype = i
+        so.bh_import_starts.argtypes = [p, ctypes.c_longlong, p, i, p, p]
+        so.bh_import_starts.restype = i
+        so.bh_import_classify.argtypes = [p, p, i] + [p] * 5
+        so.bh_import_classify.restype = i
+        so.bh_import_emit.argtypes = [p, i] + [p] * 4
+        so.bh_import_emit.restype = i
         _lib = so
     return _lib
 
