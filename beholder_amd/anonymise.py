@@ -46,8 +46,9 @@ import functools
 import hashlib
 from typing import Callable, FrozenSet, List
 
-from . import ops, replay
-from .coalesce import DROP, KEEP, UNDECODED_MODES, _spans
+from . import capture_io, ops, replay
+from .capture_io import frame_spans
+from .coalesce import DROP, KEEP, UNDECODED_MODES
 from .models import proto
 from .normalise import frame_of
 from .topics import PROGRESS_ID, STATUS_ID
@@ -179,7 +180,7 @@ def anonymise_cpu(data, policy: Policy, dialect: str = "protobufjs") -> Anonymis
     ``ValueError`` for broken framing, as ``normalise_cpu`` does."""
     anon = anon_of(policy, dialect)
     view = memoryview(data)
-    spans = list(_spans(view))
+    spans = list(frame_spans(view))
     parts, indices = [], []
     events = 0
     for i, (a, b) in enumerate(spans):
@@ -223,28 +224,18 @@ def anonymise_file(path, out, policy: Policy, device: str = "cpu", dialect: str 
     to the host."""
     _check_policy(policy)
     replay._check_dialect(dialect)
-    if device == "gpu":
-        device = "cuda"
-    if device == "cpu":
-        def cut(chunk):
-            return anonymise_cpu(chunk, policy, dialect), 0
-    else:
-        from .ops import gpu_anonymise
 
-        def cut(chunk):
-            try:
-                return gpu_anonymise.anonymise(chunk, policy, device=device, dialect=dialect)
-            except gpu_anonymise.TooLarge as e:
-                raise ValueError(f"{e}; cut smaller pieces with --chunk-bytes") from None
+    def on_device(device):
+        from .ops import gpu_anonymise
+        return capture_io.with_chunk_bytes_hint(gpu_anonymise.TooLarge, lambda chunk: gpu_anonymise.anonymise(
+            chunk, policy, device=device, dialect=dialect))
+    cut = capture_io.per_chunk(device, lambda chunk: anonymise_cpu(chunk, policy, dialect), on_device)
     counts = {"frames": 0, "kept": 0, "kept_bytes": 0, "in_bytes": 0, "events": 0, "undecoded": 0, "host_frames": 0}
-    f = open(path, "rb") if isinstance(path, (str, bytes)) or hasattr(path, "__fspath__") else path
-    try:
-        for chunk in replay.iter_chunks(f, chunk_bytes):
-            part, host_frames = cut(chunk)
+    with capture_io.open_source(path) as f:
+        for chunk, part, host_frames in capture_io.chunk_parts(f, chunk_bytes, replay.iter_chunks, cut):
             out.write(part.data)
             if indices_out is not None:
-                base = counts["frames"]
-                indices_out.write("".join(f"{base + i}\n" for i in part.indices))
+                capture_io.write_indices(indices_out, part.indices, counts["frames"])
             counts["frames"] += part.frames
             counts["kept"] += len(part.indices)
             counts["kept_bytes"] += len(part.data)
@@ -252,7 +243,4 @@ def anonymise_file(path, out, policy: Policy, device: str = "cpu", dialect: str 
             counts["events"] += part.events
             counts["undecoded"] += part.frames - part.events
             counts["host_frames"] += host_frames
-    finally:
-        if f is not path:
-            f.close()
     return counts

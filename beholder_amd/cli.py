@@ -250,22 +250,33 @@ def cmd_decode(a: argparse.Namespace) -> int:
     return 0
 
 
+def _gpu_ready(a: argparse.Namespace, module_name: str) -> bool:
+    """Whether the command can go on: true under ``--device cpu``, and under ``--device gpu`` where
+    torch, ``ops.<module_name>``, a device and the HIP library are all there. Where one is missing it
+    says so on stderr, and the command returns 1."""
+    if a.device != "gpu":
+        return True
+    import importlib
+    try:
+        import torch
+        importlib.import_module(f".ops.{module_name}", __package__)  # its imports fail here, not mid-run
+        from .ops import hip_lib
+        if not torch.cuda.is_available():
+            raise RuntimeError("no GPU is visible")
+        hip_lib.lib()
+    except (ImportError, RuntimeError, OSError) as e:
+        print(f"beholder: --device gpu is not available ({e}); use --device cpu", file=sys.stderr)
+        return False
+    return True
+
+
 def cmd_summarise(a: argparse.Namespace) -> int:
     """What the service will have done once this stream has gone through (``beholder_amd.replay``)."""
     import io
 
     from . import replay
-    if a.device == "gpu":
-        try:
-            import torch
-
-            from .ops import gpu_fold, hip_lib  # noqa: F401  gpu_fold: its imports fail here, not mid-run
-            if not torch.cuda.is_available():
-                raise RuntimeError("no GPU is visible")
-            hip_lib.lib()
-        except (ImportError, RuntimeError, OSError) as e:
-            print(f"beholder: --device gpu is not available ({e}); use --device cpu", file=sys.stderr)
-            return 1
+    if not _gpu_ready(a, "gpu_fold"):
+        return 1
     try:
         source = a.input if a.input else io.BytesIO(sys.stdin.buffer.read())
         summary = replay.fold_file(source, device=a.device, dialect=a.dialect, chunk_bytes=a.chunk_bytes)
@@ -279,26 +290,15 @@ def cmd_summarise(a: argparse.Namespace) -> int:
     return 0
 
 
-def cmd_transitions(a: argparse.Namespace) -> int:
-    """How the media of this stream got where they end: their status moves (``beholder_amd.transitions``)."""
+def _report(a: argparse.Namespace, module_name: str, report_file) -> int:
+    """A report command: ``report_file`` over the input, read whole where it is stdin, and the report
+    with its ``host_frames`` to stdout as one JSON object."""
     import io
-
-    from . import transitions
-    if a.device == "gpu":
-        try:
-            import torch
-
-            from .ops import gpu_transitions, hip_lib  # noqa: F401  gpu_transitions: its imports fail here, not mid-run
-            if not torch.cuda.is_available():
-                raise RuntimeError("no GPU is visible")
-            hip_lib.lib()
-        except (ImportError, RuntimeError, OSError) as e:
-            print(f"beholder: --device gpu is not available ({e}); use --device cpu", file=sys.stderr)
-            return 1
+    if not _gpu_ready(a, module_name):
+        return 1
     try:
         source = a.input if a.input else io.BytesIO(sys.stdin.buffer.read())
-        result, host_frames = transitions.transitions_file(source, device=a.device, dialect=a.dialect,
-                                                           chunk_bytes=a.chunk_bytes)
+        result, host_frames = report_file(source, device=a.device, dialect=a.dialect, chunk_bytes=a.chunk_bytes)
     except ValueError as e:
         print(f"beholder: {e}", file=sys.stderr)
         return 1
@@ -306,62 +306,24 @@ def cmd_transitions(a: argparse.Namespace) -> int:
     out["host_frames"] = host_frames
     print(json.dumps(out))
     return 0
+
+
+def cmd_transitions(a: argparse.Namespace) -> int:
+    """How the media of this stream got where they end: their status moves (``beholder_amd.transitions``)."""
+    from . import transitions
+    return _report(a, "gpu_transitions", transitions.transitions_file)
 
 
 def cmd_hosts(a: argparse.Namespace) -> int:
     """What every worker host did in this stream, and what it held at the end (``beholder_amd.hosts``)."""
-    import io
-
     from . import hosts
-    if a.device == "gpu":
-        try:
-            import torch
-
-            from .ops import gpu_hosts, hip_lib  # noqa: F401  gpu_hosts: its imports fail here, not mid-run
-            if not torch.cuda.is_available():
-                raise RuntimeError("no GPU is visible")
-            hip_lib.lib()
-        except (ImportError, RuntimeError, OSError) as e:
-            print(f"beholder: --device gpu is not available ({e}); use --device cpu", file=sys.stderr)
-            return 1
-    try:
-        source = a.input if a.input else io.BytesIO(sys.stdin.buffer.read())
-        result, host_frames = hosts.hosts_file(source, device=a.device, dialect=a.dialect, chunk_bytes=a.chunk_bytes)
-    except ValueError as e:
-        print(f"beholder: {e}", file=sys.stderr)
-        return 1
-    out = result.to_json(per_media=a.per_media)
-    out["host_frames"] = host_frames
-    print(json.dumps(out))
-    return 0
+    return _report(a, "gpu_hosts", hosts.hosts_file)
 
 
 def cmd_stages(a: argparse.Namespace) -> int:
     """Both topics of this stream joined per media: the stage every media is in and how far (``beholder_amd.stages``)."""
-    import io
-
     from . import stages
-    if a.device == "gpu":
-        try:
-            import torch
-
-            from .ops import gpu_stages, hip_lib  # noqa: F401  gpu_stages: its imports fail here, not mid-run
-            if not torch.cuda.is_available():
-                raise RuntimeError("no GPU is visible")
-            hip_lib.lib()
-        except (ImportError, RuntimeError, OSError) as e:
-            print(f"beholder: --device gpu is not available ({e}); use --device cpu", file=sys.stderr)
-            return 1
-    try:
-        source = a.input if a.input else io.BytesIO(sys.stdin.buffer.read())
-        result, host_frames = stages.stages_file(source, device=a.device, dialect=a.dialect, chunk_bytes=a.chunk_bytes)
-    except ValueError as e:
-        print(f"beholder: {e}", file=sys.stderr)
-        return 1
-    out = result.to_json(per_media=a.per_media)
-    out["host_frames"] = host_frames
-    print(json.dumps(out))
-    return 0
+    return _report(a, "gpu_stages", stages.stages_file)
 
 
 def _topic_byte(text: str) -> int:
@@ -402,19 +364,10 @@ def cmd_extract(a: argparse.Namespace) -> int:
     except (ValueError, OSError) as e:
         print(f"beholder: {e}", file=sys.stderr)
         return 2
-    if a.device == "gpu":
-        try:
-            import torch
-
-            from .ops import gpu_extract, hip_lib  # noqa: F401  gpu_extract: its imports fail here, not mid-run
-            if not torch.cuda.is_available():
-                raise RuntimeError("no GPU is visible")
-            hip_lib.lib()
-        except (ImportError, RuntimeError, OSError) as e:
-            print(f"beholder: --device gpu is not available ({e}); use --device cpu", file=sys.stderr)
-            return 1
+    if not _gpu_ready(a, "gpu_extract"):
+        return 1
     source = a.input if a.input else sys.stdin.buffer
-    out = sys.stdout.buffer if a.out == "-" else open(a.out, "wb")
+    out = sys.stdout.buffer if a.out == "-" else open(a.out, "wb")  # at once, not lazily: a failed run leaves its files
     indices = open(a.indices, "w", encoding="ascii") if a.indices else None
     try:
         counts = extract.extract_file(source, out, selector, device=a.device, dialect=a.dialect,
@@ -458,35 +411,56 @@ class _LazyOutput:
             self.file.close()
 
 
+def _close_outputs(outs, failed: Optional[Exception] = None) -> None:
+    """The end of a run for its :class:`_LazyOutput` files (``None`` entries are passed over). After
+    a run that went through, each is finished: one that nothing was written to becomes an empty file.
+    After one that failed, only what it had opened is closed (stdout: flushed), holding what it wrote;
+    the rest leaves no file."""
+    for f in outs:
+        if f is None:
+            continue
+        if failed is None:
+            f.finish()
+        elif f.file is not None:
+            if f.name == "-" and not f.text:
+                f.file.flush()
+            else:
+                f.file.close()
+
+
+def _rewrite(outs, run, warn=None) -> int:
+    """A stream-to-stream command from its outputs on: ``run()`` writes them and returns the counts,
+    which go to stderr as one JSON line, after what ``warn(counts)`` has to say. A ``ValueError``
+    (broken framing, a malformed row, a chunk too large for the device) is reported and gives 1; what
+    was written before it is whole frames."""
+    try:
+        counts = run()
+    except ValueError as e:
+        _close_outputs(outs, e)
+        print(f"beholder: {e}", file=sys.stderr)
+        return 1
+    _close_outputs(outs)
+    if warn is not None:
+        warn(counts)
+    print(json.dumps(counts), file=sys.stderr)
+    return 0
+
+
+def _lazy_outputs(a: argparse.Namespace, indices: Optional[str]):
+    """``(source, out, indices_out)`` of a stream-to-stream command whose ``-o`` is one file."""
+    return (a.input if a.input else sys.stdin.buffer, _LazyOutput(a.out),
+            _LazyOutput(indices, text=True) if indices else None)
+
+
 def cmd_coalesce(a: argparse.Namespace) -> int:
     """Cut a framed stream down to the frames that set its end state (``beholder_amd.coalesce``)."""
     from . import coalesce
     policy = coalesce.Policy(status=a.status, progress=a.progress, undecoded=a.undecoded)  # argparse checked the values
-    if a.device == "gpu":
-        try:
-            import torch
-
-            from .ops import gpu_coalesce, hip_lib  # noqa: F401  gpu_coalesce: its imports fail here, not mid-run
-            if not torch.cuda.is_available():
-                raise RuntimeError("no GPU is visible")
-            hip_lib.lib()
-        except (ImportError, RuntimeError, OSError) as e:
-            print(f"beholder: --device gpu is not available ({e}); use --device cpu", file=sys.stderr)
-            return 1
-    source = a.input if a.input else sys.stdin.buffer
-    out = _LazyOutput(a.out)
-    indices = _LazyOutput(a.indices, text=True) if a.indices else None
-    try:
-        counts = coalesce.coalesce_file(source, out, policy, device=a.device, dialect=a.dialect,
-                                        chunk_bytes=a.chunk_bytes, indices_out=indices)
-    except ValueError as e:  # broken framing: nothing was written
-        print(f"beholder: {e}", file=sys.stderr)
+    if not _gpu_ready(a, "gpu_coalesce"):
         return 1
-    out.finish()
-    if indices is not None:
-        indices.finish()
-    print(json.dumps(counts), file=sys.stderr)
-    return 0
+    source, out, indices = _lazy_outputs(a, a.indices)
+    return _rewrite((out, indices), lambda: coalesce.coalesce_file(  # fails before anything is written
+        source, out, policy, device=a.device, dialect=a.dialect, chunk_bytes=a.chunk_bytes, indices_out=indices))
 
 
 def cmd_dedupe(a: argparse.Namespace) -> int:
@@ -497,41 +471,11 @@ def cmd_dedupe(a: argparse.Namespace) -> int:
     except ValueError as e:
         print(f"beholder: {e}", file=sys.stderr)
         return 2
-    if a.device == "gpu":
-        try:
-            import torch
-
-            from .ops import gpu_dedupe, hip_lib  # noqa: F401  gpu_dedupe: its imports fail here, not mid-run
-            if not torch.cuda.is_available():
-                raise RuntimeError("no GPU is visible")
-            hip_lib.lib()
-        except (ImportError, RuntimeError, OSError) as e:
-            print(f"beholder: --device gpu is not available ({e}); use --device cpu", file=sys.stderr)
-            return 1
-    source = a.input if a.input else sys.stdin.buffer
-    out = _LazyOutput(a.out)
-    indices = _LazyOutput(a.indices, text=True) if a.indices else None
-    failed = None
-    try:
-        counts = dedupe.dedupe_file(source, out, policy, device=a.device, chunk_bytes=a.chunk_bytes,
-                                    indices_out=indices)
-    except ValueError as e:  # broken framing: nothing was written (last), or whole frames only (first)
-        failed = e
-    for f in (out, indices):
-        if f is None:
-            continue
-        if failed is None:
-            f.finish()
-        elif f.file is not None:
-            if f.name == "-" and not f.text:
-                f.file.flush()
-            else:
-                f.file.close()
-    if failed is not None:
-        print(f"beholder: {failed}", file=sys.stderr)
+    if not _gpu_ready(a, "gpu_dedupe"):
         return 1
-    print(json.dumps(counts), file=sys.stderr)
-    return 0
+    source, out, indices = _lazy_outputs(a, a.indices)
+    return _rewrite((out, indices), lambda: dedupe.dedupe_file(  # last: fails before anything is written
+        source, out, policy, device=a.device, chunk_bytes=a.chunk_bytes, indices_out=indices))
 
 
 def cmd_compare(a: argparse.Namespace) -> int:
@@ -542,17 +486,8 @@ def cmd_compare(a: argparse.Namespace) -> int:
     except ValueError as e:
         print(f"beholder: {e}", file=sys.stderr)
         return 2
-    if a.device == "gpu":
-        try:
-            import torch
-
-            from .ops import gpu_compare, hip_lib  # noqa: F401  gpu_compare: its imports fail here, not mid-run
-            if not torch.cuda.is_available():
-                raise RuntimeError("no GPU is visible")
-            hip_lib.lib()
-        except (ImportError, RuntimeError, OSError) as e:
-            print(f"beholder: --device gpu is not available ({e}); use --device cpu", file=sys.stderr)
-            return 1
+    if not _gpu_ready(a, "gpu_compare"):
+        return 1
     outs = [_LazyOutput(name, text=text) if name else None
             for name, text in ((a.only_a, False), (a.only_b, False), (a.indices_a, True), (a.indices_b, True))]
     try:
@@ -561,10 +496,8 @@ def cmd_compare(a: argparse.Namespace) -> int:
     except (ValueError, OSError) as e:  # broken framing, captures beyond the device's limit: nothing was written
         print(f"beholder: {e}", file=sys.stderr)
         return 1
-    for f in outs:
-        if f is not None:
-            f.finish()
-    print(json.dumps(counts))
+    _close_outputs(outs)
+    print(json.dumps(counts))  # to stdout: the counts are this command's result
     return 3 if a.exit_code and not counts["equal"] else 0
 
 
@@ -576,82 +509,22 @@ def cmd_thin(a: argparse.Namespace) -> int:
     except ValueError as e:
         print(f"beholder: {e}", file=sys.stderr)
         return 2
-    if a.device == "gpu":
-        try:
-            import torch
-
-            from .ops import gpu_thin, hip_lib  # noqa: F401  gpu_thin: its imports fail here, not mid-run
-            if not torch.cuda.is_available():
-                raise RuntimeError("no GPU is visible")
-            hip_lib.lib()
-        except (ImportError, RuntimeError, OSError) as e:
-            print(f"beholder: --device gpu is not available ({e}); use --device cpu", file=sys.stderr)
-            return 1
-    source = a.input if a.input else sys.stdin.buffer
-    out = _LazyOutput(a.out)
-    indices = _LazyOutput(a.indices, text=True) if a.indices else None
-    failed = None
-    try:
-        counts = thin.thin_file(source, out, policy, device=a.device, dialect=a.dialect, chunk_bytes=a.chunk_bytes,
-                                indices_out=indices)
-    except ValueError as e:  # broken framing: nothing was written (last), or whole frames only (first)
-        failed = e
-    for f in (out, indices):
-        if f is None:
-            continue
-        if failed is None:
-            f.finish()
-        elif f.file is not None:
-            if f.name == "-" and not f.text:
-                f.file.flush()
-            else:
-                f.file.close()
-    if failed is not None:
-        print(f"beholder: {failed}", file=sys.stderr)
+    if not _gpu_ready(a, "gpu_thin"):
         return 1
-    print(json.dumps(counts), file=sys.stderr)
-    return 0
+    source, out, indices = _lazy_outputs(a, a.indices)
+    return _rewrite((out, indices), lambda: thin.thin_file(  # last: fails before anything is written
+        source, out, policy, device=a.device, dialect=a.dialect, chunk_bytes=a.chunk_bytes, indices_out=indices))
 
 
 def cmd_normalise(a: argparse.Namespace) -> int:
     """Rewrite every decodable event of a framed stream in canonical form (``beholder_amd.normalise``)."""
     from . import normalise
     policy = normalise.Policy(undecoded=a.undecoded)  # argparse checked the value
-    if a.device == "gpu":
-        try:
-            import torch
-
-            from .ops import gpu_normalise, hip_lib  # noqa: F401  gpu_normalise: its imports fail here, not mid-run
-            if not torch.cuda.is_available():
-                raise RuntimeError("no GPU is visible")
-            hip_lib.lib()
-        except (ImportError, RuntimeError, OSError) as e:
-            print(f"beholder: --device gpu is not available ({e}); use --device cpu", file=sys.stderr)
-            return 1
-    source = a.input if a.input else sys.stdin.buffer
-    out = _LazyOutput(a.out)
-    indices = _LazyOutput(a.indices, text=True) if a.indices else None
-    failed = None
-    try:
-        counts = normalise.normalise_file(source, out, policy, device=a.device, dialect=a.dialect,
-                                          chunk_bytes=a.chunk_bytes, indices_out=indices)
-    except ValueError as e:  # broken framing, or a chunk too large for the device: whole frames only were written
-        failed = e
-    for f in (out, indices):
-        if f is None:
-            continue
-        if failed is None:
-            f.finish()
-        elif f.file is not None:
-            if f.name == "-" and not f.text:
-                f.file.flush()
-            else:
-                f.file.close()
-    if failed is not None:
-        print(f"beholder: {failed}", file=sys.stderr)
+    if not _gpu_ready(a, "gpu_normalise"):
         return 1
-    print(json.dumps(counts), file=sys.stderr)
-    return 0
+    source, out, indices = _lazy_outputs(a, a.indices)
+    return _rewrite((out, indices), lambda: normalise.normalise_file(
+        source, out, policy, device=a.device, dialect=a.dialect, chunk_bytes=a.chunk_bytes, indices_out=indices))
 
 
 ANONYMISE_KEY_ENV = "BEHOLDER_ANONYMISE_KEY"
@@ -706,125 +579,38 @@ def cmd_anonymise(a: argparse.Namespace) -> int:
         for field, value in requests:
             print(f"{field}\t{value}\t{anonymise.pseudonym_of(policy.key, field, value)}")
         return 0
-    if a.device == "gpu":
-        try:
-            import torch
-
-            from .ops import gpu_anonymise, hip_lib  # noqa: F401  gpu_anonymise: its imports fail here, not mid-run
-            if not torch.cuda.is_available():
-                raise RuntimeError("no GPU is visible")
-            hip_lib.lib()
-        except (ImportError, RuntimeError, OSError) as e:
-            print(f"beholder: --device gpu is not available ({e}); use --device cpu", file=sys.stderr)
-            return 1
-    source = a.input if a.input else sys.stdin.buffer
-    out = _LazyOutput(a.out)
-    indices = _LazyOutput(a.indices, text=True) if a.indices else None
-    failed = None
-    try:
-        counts = anonymise.anonymise_file(source, out, policy, device=a.device, dialect=a.dialect,
-                                          chunk_bytes=a.chunk_bytes, indices_out=indices)
-    except ValueError as e:  # broken framing, or a chunk too large for the device: whole frames only were written
-        failed = e
-    for f in (out, indices):
-        if f is None:
-            continue
-        if failed is None:
-            f.finish()
-        elif f.file is not None:
-            if f.name == "-" and not f.text:
-                f.file.flush()
-            else:
-                f.file.close()
-    if failed is not None:
-        print(f"beholder: {failed}", file=sys.stderr)
+    if not _gpu_ready(a, "gpu_anonymise"):
         return 1
-    if policy.undecoded == "keep" and counts["undecoded"]:
-        print(f"beholder: warning: {counts['undecoded']} undecoded frames were kept byte for byte; they may hold "
-              "names in clear", file=sys.stderr)
-    print(json.dumps(counts), file=sys.stderr)
-    return 0
+
+    def warn(counts: dict) -> None:
+        if policy.undecoded == "keep" and counts["undecoded"]:
+            print(f"beholder: warning: {counts['undecoded']} undecoded frames were kept byte for byte; they may hold "
+                  "names in clear", file=sys.stderr)
+    source, out, indices = _lazy_outputs(a, a.indices)
+    return _rewrite((out, indices), lambda: anonymise.anonymise_file(
+        source, out, policy, device=a.device, dialect=a.dialect, chunk_bytes=a.chunk_bytes, indices_out=indices), warn)
 
 
 def cmd_export(a: argparse.Namespace) -> int:
     """Write a framed stream as NDJSON rows, one per frame (``beholder_amd.export``)."""
     from . import export
     policy = export.Policy(undecoded=a.undecoded)  # argparse checked the value
-    if a.device == "gpu":
-        try:
-            import torch
-
-            from .ops import gpu_export, hip_lib  # noqa: F401  gpu_export: its imports fail here, not mid-run
-            if not torch.cuda.is_available():
-                raise RuntimeError("no GPU is visible")
-            hip_lib.lib()
-        except (ImportError, RuntimeError, OSError) as e:
-            print(f"beholder: --device gpu is not available ({e}); use --device cpu", file=sys.stderr)
-            return 1
-    source = a.input if a.input else sys.stdin.buffer
-    out = _LazyOutput(a.out)
-    indices = _LazyOutput(a.indices, text=True) if a.indices else None
-    failed = None
-    try:
-        counts = export.export_file(source, out, policy, device=a.device, dialect=a.dialect, chunk_bytes=a.chunk_bytes,
-                                    indices_out=indices)
-    except ValueError as e:  # broken framing, or a chunk too large for the device: whole rows only were written
-        failed = e
-    for f in (out, indices):
-        if f is None:
-            continue
-        if failed is None:
-            f.finish()
-        elif f.file is not None:
-            if f.name == "-" and not f.text:
-                f.file.flush()
-            else:
-                f.file.close()
-    if failed is not None:
-        print(f"beholder: {failed}", file=sys.stderr)
+    if not _gpu_ready(a, "gpu_export"):
         return 1
-    print(json.dumps(counts), file=sys.stderr)
-    return 0
+    source, out, indices = _lazy_outputs(a, a.indices)
+    return _rewrite((out, indices), lambda: export.export_file(  # what a failed run wrote is whole rows
+        source, out, policy, device=a.device, dialect=a.dialect, chunk_bytes=a.chunk_bytes, indices_out=indices))
 
 
 def cmd_import(a: argparse.Namespace) -> int:
     """Read NDJSON rows back into a framed stream (``beholder_amd.import_rows``)."""
     from . import import_rows
     policy = import_rows.Policy(malformed=a.malformed)  # argparse checked the value
-    if a.device == "gpu":
-        try:
-            import torch
-
-            from .ops import gpu_import, hip_lib  # noqa: F401  gpu_import: its imports fail here, not mid-run
-            if not torch.cuda.is_available():
-                raise RuntimeError("no GPU is visible")
-            hip_lib.lib()
-        except (ImportError, RuntimeError, OSError) as e:
-            print(f"beholder: --device gpu is not available ({e}); use --device cpu", file=sys.stderr)
-            return 1
-    source = a.input if a.input else sys.stdin.buffer
-    out = _LazyOutput(a.out)
-    lines = _LazyOutput(a.lines, text=True) if a.lines else None
-    failed = None
-    try:
-        counts = import_rows.import_file(source, out, policy, device=a.device, chunk_bytes=a.chunk_bytes, lines_out=lines)
-    except ValueError as e:  # a malformed row, or a chunk too large for the device: whole frames only were written
-        failed = e
-    for f in (out, lines):
-        if f is None:
-            continue
-        if failed is None:
-            f.finish()
-        elif f.file is not None:
-            if f.name == "-" and not f.text:
-                f.file.flush()
-            else:
-                f.file.close()
-    if failed is not None:
-        print(f"beholder: {failed}", file=sys.stderr)
+    if not _gpu_ready(a, "gpu_import"):
         return 1
-    print(json.dumps(counts), file=sys.stderr)
-    return 0
+    source, out, lines = _lazy_outputs(a, a.lines)
+    return _rewrite((out, lines), lambda: import_rows.import_file(
+        source, out, policy, device=a.device, chunk_bytes=a.chunk_bytes, lines_out=lines))
 
 
 def cmd_shard(a: argparse.Namespace) -> int:
@@ -838,37 +624,15 @@ def cmd_shard(a: argparse.Namespace) -> int:
     except ValueError as e:
         print(f"beholder: {e}", file=sys.stderr)
         return 2
-    if a.device == "gpu":
-        try:
-            import torch
-
-            from .ops import gpu_shard, hip_lib  # noqa: F401  gpu_shard: its imports fail here, not mid-run
-            if not torch.cuda.is_available():
-                raise RuntimeError("no GPU is visible")
-            hip_lib.lib()
-        except (ImportError, RuntimeError, OSError) as e:
-            print(f"beholder: --device gpu is not available ({e}); use --device cpu", file=sys.stderr)
-            return 1
+    if not _gpu_ready(a, "gpu_shard"):
+        return 1
     source = a.input if a.input else sys.stdin.buffer
     outs = [_LazyOutput(a.out.replace("{}", str(s))) for s in range(policy.shards)]
     indices = [_LazyOutput(a.indices.replace("{}", str(s)), text=True) for s in range(policy.shards)] \
         if a.indices else None
-    failed = None
-    try:
-        counts = shard.shard_file(source, outs, policy, device=a.device, dialect=a.dialect,
-                                  chunk_bytes=a.chunk_bytes, indices_outs=indices)
-    except ValueError as e:  # broken framing: what was written so far is whole frames
-        failed = e
-    for f in outs + (indices or []):
-        if failed is None:
-            f.finish()  # every shard gets a file, an empty one included
-        elif f.file is not None:
-            f.file.close()
-    if failed is not None:
-        print(f"beholder: {failed}", file=sys.stderr)
-        return 1
-    print(json.dumps(counts), file=sys.stderr)
-    return 0
+    # after a run that went through every shard gets a file, an empty one included
+    return _rewrite(outs + (indices or []), lambda: shard.shard_file(
+        source, outs, policy, device=a.device, dialect=a.dialect, chunk_bytes=a.chunk_bytes, indices_outs=indices))
 
 
 def cmd_seed(a: argparse.Namespace) -> int:
@@ -906,6 +670,34 @@ def cmd_publish(a: argparse.Namespace) -> int:
     n = asyncio.run(publish_frames(a.url, data))
     print(n)
     return 0
+
+
+def _device_arg(p: argparse.ArgumentParser, kernels: str) -> None:
+    p.add_argument("--device", choices=["cpu", "gpu"], default="cpu",
+                   help=f"cpu: the definition, runs anywhere; gpu: the gfx950 {kernels} kernels")
+
+
+def _capture_args(p: argparse.ArgumentParser, kernels: str, chunk_help: Optional[str], chunk_default: int = 256 << 20,
+                  dialect: bool = True) -> None:
+    """What the capture commands share, in the order their help lists it: the input, ``--device``
+    (``kernels`` names its kernel family), ``--dialect`` and, where ``chunk_help`` is given,
+    ``--chunk-bytes``. A command's own options that come before these are added before the call."""
+    p.add_argument("input", nargs="?")
+    _device_arg(p, kernels)
+    if dialect:
+        p.add_argument("--dialect", choices=["protobufjs", "upb"], default="protobufjs")
+    if chunk_help:
+        p.add_argument("--chunk-bytes", type=int, default=chunk_default, help=chunk_help)
+
+
+def _indices_arg(p: argparse.ArgumentParser, help: str, metavar: str = "FILE") -> None:
+    p.add_argument("--indices", metavar=metavar, help=help)
+
+
+CUT_HELP = "cut the input in pieces of this size"
+READ_HELP = "read the input in pieces of this size"
+KEPT_INDICES_HELP = "write the kept frames' input indices here, one per line"
+OUTPUT_INDICES_HELP = "write the output frames' input indices here, one per line"
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -952,10 +744,7 @@ def build_parser() -> argparse.ArgumentParser:
     d.set_defaults(fn=cmd_decode)
 
     z = sub.add_parser("summarise", help="framed stream -> what the service will have done with it (JSON)")
-    z.add_argument("input", nargs="?")
-    z.add_argument("--device", choices=["cpu", "gpu"], default="cpu",
-                   help="cpu: the definition, runs anywhere; gpu: the gfx950 fold kernels")
-    z.add_argument("--dialect", choices=["protobufjs", "upb"], default="protobufjs")
+    _capture_args(z, "fold", chunk_help=None)  # --chunk-bytes comes after the command's own option
     z.add_argument("--media-fixture", help="JSON list of media rows: also print the prediction for them")
     z.add_argument("--chunk-bytes", type=int, default=256 << 20, help="fold the input in pieces of this size")
     z.set_defaults(fn=cmd_summarise)
@@ -964,11 +753,7 @@ def build_parser() -> argparse.ArgumentParser:
                        description="Count, over every media's status events in stream order, the moves between "
                                    "status classes: the transition matrix, changes, repeats, and the classes "
                                    "the media start and end on. Prints one JSON object.")
-    t.add_argument("input", nargs="?")
-    t.add_argument("--device", choices=["cpu", "gpu"], default="cpu",
-                   help="cpu: the definition, runs anywhere; gpu: the gfx950 transitions kernels")
-    t.add_argument("--dialect", choices=["protobufjs", "upb"], default="protobufjs")
-    t.add_argument("--chunk-bytes", type=int, default=256 << 20, help="read the input in pieces of this size")
+    _capture_args(t, "transitions", READ_HELP)
     t.add_argument("--per-media", action="store_true", help="also print one row per mediaId")
     t.set_defaults(fn=cmd_transitions)
 
@@ -976,11 +761,7 @@ def build_parser() -> argparse.ArgumentParser:
                        description="Count, per worker host of the progress events, its events, media, stints, "
                                    "the media it took over and lost, its rewinds, and the media it held when the "
                                    "stream ended, by status. Prints one JSON object.")
-    w.add_argument("input", nargs="?")
-    w.add_argument("--device", choices=["cpu", "gpu"], default="cpu",
-                   help="cpu: the definition, runs anywhere; gpu: the gfx950 hosts kernels")
-    w.add_argument("--dialect", choices=["protobufjs", "upb"], default="protobufjs")
-    w.add_argument("--chunk-bytes", type=int, default=256 << 20, help="read the input in pieces of this size")
+    _capture_args(w, "hosts", READ_HELP)
     w.add_argument("--per-media", action="store_true", help="also print one row per mediaId")
     w.set_defaults(fn=cmd_hosts)
 
@@ -989,18 +770,13 @@ def build_parser() -> argparse.ArgumentParser:
                                    "class, the progress events by standing and reported status, the closed and the "
                                    "open stages by status and progress bucket, and the progress events that come "
                                    "before their media's first status event. Prints one JSON object.")
-    g.add_argument("input", nargs="?")
-    g.add_argument("--device", choices=["cpu", "gpu"], default="cpu",
-                   help="cpu: the definition, runs anywhere; gpu: the gfx950 stages kernels")
-    g.add_argument("--dialect", choices=["protobufjs", "upb"], default="protobufjs")
-    g.add_argument("--chunk-bytes", type=int, default=256 << 20, help="read the input in pieces of this size")
+    _capture_args(g, "stages", READ_HELP)
     g.add_argument("--per-media", action="store_true", help="also print one row per mediaId")
     g.set_defaults(fn=cmd_stages)
 
     x = sub.add_parser("extract", help="framed stream -> the selected frames, a framed stream again",
                        description="Keep the frames that meet every given condition (none: all frames); "
                                    "the counts go to stderr as one JSON line.")
-    x.add_argument("input", nargs="?")
     x.add_argument("-o", "--out", required=True, help="output file ('-' for stdout)")
     x.add_argument("--topic", action="append", metavar="status|progress|N", help="topic byte; repeatable")
     x.add_argument("--outcome", action="append", choices=["decoded", "error", "other"],
@@ -1012,27 +788,21 @@ def build_parser() -> argparse.ArgumentParser:
     x.add_argument("--unknown-status", action="store_true",
                    help="a decoded frame whose status is no TelemetryStatusEntry number (quirk Q6)")
     x.add_argument("--invert", action="store_true", help="keep exactly the frames the rest rejects")
-    x.add_argument("--device", choices=["cpu", "gpu"], default="cpu",
-                   help="cpu: the definition, runs anywhere; gpu: the gfx950 select kernels")
-    x.add_argument("--dialect", choices=["protobufjs", "upb"], default="protobufjs")
-    x.add_argument("--chunk-bytes", type=int, default=256 << 20, help="cut the input in pieces of this size")
-    x.add_argument("--indices", metavar="FILE", help="write the kept frames' input indices here, one per line")
+    _capture_args(x, "select", CUT_HELP)
+    _indices_arg(x, KEPT_INDICES_HELP)
     x.set_defaults(fn=cmd_extract)
 
     u = sub.add_parser("dedupe", help="framed stream -> the same without byte-identical repeat frames",
                        description="Keep one frame of every distinct content (topic byte and body), by default "
                                    "the last, which is the one that is safe to replay; nothing is decoded. "
                                    "The counts go to stderr as one JSON line.")
-    u.add_argument("input", nargs="?")
     u.add_argument("-o", "--out", required=True, help="output file ('-' for stdout)")
     u.add_argument("--keep", choices=["last", "first"], default="last",
                    help="which occurrence of a content survives; 'first' can end a replay on a stale status")
     u.add_argument("--topic", action="append", metavar="status|progress|N",
                    help="only frames of this topic byte take part, the others are kept as they are; repeatable")
-    u.add_argument("--device", choices=["cpu", "gpu"], default="cpu",
-                   help="cpu: the definition, runs anywhere; gpu: the gfx950 dedupe kernels")
-    u.add_argument("--chunk-bytes", type=int, default=256 << 20, help="cut the input in pieces of this size")
-    u.add_argument("--indices", metavar="FILE", help="write the kept frames' input indices here, one per line")
+    _capture_args(u, "dedupe", CUT_HELP, dialect=False)  # nothing is decoded
+    _indices_arg(u, KEPT_INDICES_HELP)
     u.set_defaults(fn=cmd_dedupe)
 
     h = sub.add_parser("thin", help="framed stream -> the same without the progress events that repeat their step",
@@ -1040,23 +810,18 @@ def build_parser() -> argparse.ArgumentParser:
                                    "events of one mediaId with the same status and the same progress // STEP, one "
                                    "survives, by default the last. Every other frame is kept as it is. "
                                    "The counts go to stderr as one JSON line.")
-    h.add_argument("input", nargs="?")
     h.add_argument("-o", "--out", required=True, help="output file ('-' for stdout)")
     h.add_argument("--step", type=int, default=10, help="the width of a step in percentage points (1..2^31-1)")
     h.add_argument("--keep", choices=["last", "first"], default="last",
                    help="which event of a stretch of one step survives; 'last' keeps every stage's last event")
-    h.add_argument("--device", choices=["cpu", "gpu"], default="cpu",
-                   help="cpu: the definition, runs anywhere; gpu: the gfx950 thin kernels")
-    h.add_argument("--dialect", choices=["protobufjs", "upb"], default="protobufjs")
-    h.add_argument("--chunk-bytes", type=int, default=256 << 20, help="cut the input in pieces of this size")
-    h.add_argument("--indices", metavar="FILE", help="write the kept frames' input indices here, one per line")
+    _capture_args(h, "thin", CUT_HELP)
+    _indices_arg(h, KEPT_INDICES_HELP)
     h.set_defaults(fn=cmd_thin)
 
     o = sub.add_parser("coalesce", help="framed stream -> the frames that set its end state, a framed stream again",
                        description="Keep, per key, the last frame only: by default the last status event and the "
                                    "last progress event of every mediaId, and every frame that is neither. "
                                    "The counts go to stderr as one JSON line.")
-    o.add_argument("input", nargs="?")
     o.add_argument("-o", "--out", required=True, help="output file ('-' for stdout)")
     o.add_argument("--status", choices=["last", "all"], default="last",
                    help="decoded status events: the last per mediaId, or all of them")
@@ -1065,11 +830,8 @@ def build_parser() -> argparse.ArgumentParser:
                         "all (keeps beholder_progress_updates_total whole) or none")
     o.add_argument("--undecoded", choices=["keep", "drop"], default="keep",
                    help="frames that fail to decode or carry another topic byte")
-    o.add_argument("--device", choices=["cpu", "gpu"], default="cpu",
-                   help="cpu: the definition, runs anywhere; gpu: the gfx950 coalesce kernels")
-    o.add_argument("--dialect", choices=["protobufjs", "upb"], default="protobufjs")
-    o.add_argument("--chunk-bytes", type=int, default=256 << 20, help="cut the input in pieces of this size")
-    o.add_argument("--indices", metavar="FILE", help="write the kept frames' input indices here, one per line")
+    _capture_args(o, "coalesce", CUT_HELP)
+    _indices_arg(o, KEPT_INDICES_HELP)
     o.set_defaults(fn=cmd_coalesce)
 
     z = sub.add_parser("normalise", help="framed stream -> the same with every event in its canonical encoding",
@@ -1077,15 +839,11 @@ def build_parser() -> argparse.ArgumentParser:
                                    "and write it as the service's own encoder would: fields in order, defaults "
                                    "omitted, unknown fields gone. Run it first, before dedupe. "
                                    "The counts go to stderr as one JSON line.")
-    z.add_argument("input", nargs="?")
     z.add_argument("-o", "--out", default="-", help="output file (default '-': stdout)")
     z.add_argument("--undecoded", choices=["keep", "drop"], default="keep",
                    help="frames that fail to decode or carry another topic byte: as they are, or nowhere")
-    z.add_argument("--device", choices=["cpu", "gpu"], default="cpu",
-                   help="cpu: the definition, runs anywhere; gpu: the gfx950 normalise kernels")
-    z.add_argument("--dialect", choices=["protobufjs", "upb"], default="protobufjs")
-    z.add_argument("--chunk-bytes", type=int, default=256 << 20, help="cut the input in pieces of this size")
-    z.add_argument("--indices", metavar="FILE", help="write the output frames' input indices here, one per line")
+    _capture_args(z, "normalise", CUT_HELP)
+    _indices_arg(z, OUTPUT_INDICES_HELP)
     z.set_defaults(fn=cmd_normalise)
 
     y = sub.add_parser("anonymise", help="framed stream -> the same with every mediaId and host a keyed pseudonym",
@@ -1095,7 +853,6 @@ def build_parser() -> argparse.ArgumentParser:
                                    "reports of the output are the input's up to renaming. The key comes from "
                                    "--key-file, $BEHOLDER_ANONYMISE_KEY (hex) or --random-key, exactly one. "
                                    "The counts go to stderr as one JSON line.")
-    y.add_argument("input", nargs="?")
     y.add_argument("-o", "--out", default="-", help="output file (default '-': stdout)")
     y.add_argument("--key-file", metavar="PATH", help="the key: this file's bytes as they are, 16 to 32")
     y.add_argument("--random-key", action="store_true",
@@ -1107,11 +864,8 @@ def build_parser() -> argparse.ArgumentParser:
     y.add_argument("--keep-host", action="store_true", help="leave host in clear")
     y.add_argument("--pseudonym-of", action="append", metavar="mediaId=VALUE|host=VALUE",
                    help="print field, value and pseudonym, tab-separated, and read no capture; repeatable")
-    y.add_argument("--device", choices=["cpu", "gpu"], default="cpu",
-                   help="cpu: the definition, runs anywhere; gpu: the gfx950 anonymise kernels")
-    y.add_argument("--dialect", choices=["protobufjs", "upb"], default="protobufjs")
-    y.add_argument("--chunk-bytes", type=int, default=256 << 20, help="cut the input in pieces of this size")
-    y.add_argument("--indices", metavar="FILE", help="write the output frames' input indices here, one per line")
+    _capture_args(y, "anonymise", CUT_HELP)
+    _indices_arg(y, OUTPUT_INDICES_HELP)
     y.set_defaults(fn=cmd_anonymise)
 
     x = sub.add_parser("export", help="framed stream -> NDJSON rows, one per frame, for jq, DuckDB, pandas and grep",
@@ -1120,16 +874,11 @@ def build_parser() -> argparse.ArgumentParser:
                                    "its fields with the status name, or the body as base64 where it does not "
                                    "decode. The rows are NDJSON input to the service again. "
                                    "The counts go to stderr as one JSON line.")
-    x.add_argument("input", nargs="?")
     x.add_argument("-o", "--out", default="-", help="output file (default '-': stdout)")
     x.add_argument("--undecoded", choices=["keep", "drop"], default="keep",
                    help="frames that fail to decode or carry another topic byte: a base64 row, or none")
-    x.add_argument("--device", choices=["cpu", "gpu"], default="cpu",
-                   help="cpu: the definition, runs anywhere; gpu: the gfx950 export kernels")
-    x.add_argument("--dialect", choices=["protobufjs", "upb"], default="protobufjs")
-    x.add_argument("--chunk-bytes", type=int, default=64 << 20,
-                   help="cut the input in pieces of this size (the rows take several times the input's bytes)")
-    x.add_argument("--indices", metavar="FILE", help="write the rows' frame indices here, one per line")
+    _capture_args(x, "export", CUT_HELP + " (the rows take several times the input's bytes)", chunk_default=64 << 20)
+    _indices_arg(x, "write the rows' frame indices here, one per line")
     x.set_defaults(fn=cmd_export)
 
     im = sub.add_parser("import", help="NDJSON rows -> framed stream: the inverse of export",
@@ -1138,14 +887,10 @@ def build_parser() -> argparse.ArgumentParser:
                                     "fields in the canonical encoding. import of an export is the capture's "
                                     "normalise. Blank lines are passed over. "
                                     "The counts go to stderr as one JSON line.")
-    im.add_argument("input", nargs="?")
     im.add_argument("-o", "--out", default="-", help="output file (default '-': stdout)")
     im.add_argument("--malformed", choices=["fail", "skip"], default="fail",
                    help="a line that is no row: stop there with its line number and exit 1, or leave it out and count it")
-    im.add_argument("--device", choices=["cpu", "gpu"], default="cpu",
-                   help="cpu: the definition, runs anywhere; gpu: the gfx950 import kernels")
-    im.add_argument("--chunk-bytes", type=int, default=256 << 20,
-                   help="cut the input after the last newline within this size")
+    _capture_args(im, "import", "cut the input after the last newline within this size", dialect=False)
     im.add_argument("--lines", metavar="FILE", help="write the line numbers of the rows that became frames here, one per line")
     im.set_defaults(fn=cmd_import)
 
@@ -1153,18 +898,13 @@ def build_parser() -> argparse.ArgumentParser:
                        description="Every mediaId's events go to one shard, in their original order; the shard "
                                    "is a function of the decoded mediaId and N alone. "
                                    "The counts go to stderr as one JSON line.")
-    h.add_argument("input", nargs="?")
     h.add_argument("--shards", type=int, required=True, metavar="N", help="how many streams, 1-256")
     h.add_argument("-o", "--out", required=True, metavar="PATTERN",
                    help="output files; '{}' becomes the shard number ('dlq-{}.bin')")
     h.add_argument("--undecoded", choices=["first", "drop"], default="first",
                    help="frames that fail to decode or carry another topic byte: to shard 0, or nowhere")
-    h.add_argument("--device", choices=["cpu", "gpu"], default="cpu",
-                   help="cpu: the definition, runs anywhere; gpu: the gfx950 shard kernels")
-    h.add_argument("--dialect", choices=["protobufjs", "upb"], default="protobufjs")
-    h.add_argument("--chunk-bytes", type=int, default=256 << 20, help="cut the input in pieces of this size")
-    h.add_argument("--indices", metavar="PATTERN",
-                   help="write each shard's input indices to these files, one per line; '{}' as in -o")
+    _capture_args(h, "shard", CUT_HELP)
+    _indices_arg(h, "write each shard's input indices to these files, one per line; '{}' as in -o", metavar="PATTERN")
     h.set_defaults(fn=cmd_shard)
 
     m = sub.add_parser("compare", help="two framed streams -> what is only in one, what is in both, in what order",
@@ -1181,8 +921,7 @@ def build_parser() -> argparse.ArgumentParser:
     m.add_argument("--only-b", metavar="PATH", help="write the frames only in B here, a framed stream")
     m.add_argument("--indices-a", metavar="PATH", help="write the indices in A of the frames only in A, one per line")
     m.add_argument("--indices-b", metavar="PATH", help="write the indices in B of the frames only in B, one per line")
-    m.add_argument("--device", choices=["cpu", "gpu"], default="cpu",
-                   help="cpu: the definition, runs anywhere; gpu: the gfx950 compare kernels")
+    _device_arg(m, "compare")
     m.add_argument("--exit-code", action="store_true", help="exit with status 3 where the captures differ")
     m.set_defaults(fn=cmd_compare)
 

@@ -24,10 +24,10 @@ is idempotent: the coalesced stream coalesces to itself.
 from __future__ import annotations
 
 import dataclasses
-import struct
 from typing import Callable, Iterator, List, Optional, Tuple
 
-from . import ops, replay
+from . import capture_io, ops, replay
+from .capture_io import frame_spans as _spans  # the name it had here: test_thin and test_normalise import it
 from .models import proto
 from .topics import PROGRESS_ID, STATUS_ID
 
@@ -55,21 +55,6 @@ class Policy:
                 raise TypeError(f"{name} is a string, not {type(value).__name__}")
             if value not in allowed:
                 raise ValueError(f"unknown {name} policy {value!r} ({'|'.join(allowed)})")
-
-
-def _spans(data) -> Iterator[Tuple[int, int]]:
-    """``(start, end)`` of every frame of a framed stream. Raises ``ValueError`` for broken framing,
-    as ``iter_frames`` does."""
-    view = memoryview(data)
-    i, n = 0, len(view)
-    while i < n:
-        if n - i < 4:
-            raise ValueError("truncated frame header")
-        (length,) = struct.unpack_from("<I", view, i)
-        if length == 0 or n - i - 4 < length:
-            raise ValueError("truncated or empty frame")
-        yield i, i + 4 + length
-        i += 4 + length
 
 
 @dataclasses.dataclass
@@ -212,28 +197,18 @@ def coalesce_file(path, out, policy: Policy = Policy(), device: str = "cpu", dia
     Returns ``{frames, kept, kept_bytes, keys, host_frames}``: ``keys`` counts the distinct keys of
     the result, ``host_frames`` the frames a device run left to the host."""
     replay._check_dialect(dialect)
-    if device == "gpu":
-        device = "cuda"
-    if device == "cpu":
-        def cut(chunk):
-            return coalesce_cpu(chunk, policy, dialect), 0
-    else:
-        from .ops import gpu_coalesce
 
-        def cut(chunk):
-            return gpu_coalesce.coalesce(chunk, policy, device=device, dialect=dialect)
+    def on_device(device):
+        from .ops import gpu_coalesce
+        return lambda chunk: gpu_coalesce.coalesce(chunk, policy, device=device, dialect=dialect)
+    cut = capture_io.per_chunk(device, lambda chunk: coalesce_cpu(chunk, policy, dialect), on_device)
     acc = _Accumulator()
     frames = host = 0
-    f = open(path, "rb") if isinstance(path, (str, bytes)) or hasattr(path, "__fspath__") else path
-    try:
-        for chunk in replay.iter_chunks(f, chunk_bytes):
-            part, host_frames = cut(chunk)
+    with capture_io.open_source(path) as f:
+        for _, part, host_frames in capture_io.chunk_parts(f, chunk_bytes, replay.iter_chunks, cut):
             acc.add(part, frames)
             frames += part.frames
             host += host_frames
-    finally:
-        if f is not path:
-            f.close()
     kept = kept_bytes = 0
     for frame, i in acc.live():
         out.write(frame)

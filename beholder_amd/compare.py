@@ -41,7 +41,8 @@ import dataclasses
 import os
 from typing import FrozenSet, List, Optional
 
-from .coalesce import _spans
+from . import capture_io
+from .capture_io import frame_spans
 
 SHARD_ROUTE = ("shard both captures with the same `shard --shards N` and compare shard by shard: "
                "equal contents land in equal shard numbers, so the per-shard counts add up exactly")
@@ -124,7 +125,7 @@ def _occurrences(view, spans, policy: Policy) -> dict:
 def _spans_of(data, side: str):
     view = memoryview(data)
     try:
-        return view, list(_spans(view))
+        return view, list(frame_spans(view))
     except ValueError as e:
         raise ValueError(f"capture {side}: {e}") from None
 
@@ -170,10 +171,8 @@ def compare_gpu(a, b, policy: Policy = Policy(), device="cuda", hash_mask: Optio
 
 
 def _read(path) -> bytes:
-    if isinstance(path, (str, bytes)) or hasattr(path, "__fspath__"):
-        with open(path, "rb") as f:
-            return f.read()
-    return path.read()
+    with capture_io.open_source(path) as f:
+        return f.read()
 
 
 def device_limit_error(bytes_a: int, bytes_b: int, frames: Optional[int] = None) -> Optional[str]:
@@ -210,8 +209,7 @@ def compare_file(path_a, path_b, only_a_out=None, only_b_out=None, policy: Polic
     only_b_bytes, distinct_a, distinct_b, distinct_common, order_breaks, equal, host_frames}``;
     ``host_frames`` counts the frames a device run left to the host."""
     _check_policy(policy)
-    if device == "gpu":
-        device = "cuda"
+    device = capture_io.torch_device(device)
     if device != "cpu":
         sizes = []
         for path in (path_a, path_b):
@@ -231,5 +229,5 @@ def compare_file(path_a, path_b, only_a_out=None, only_b_out=None, policy: Polic
         if out is not None:
             out.write(side.data)
         if indices_out is not None:
-            indices_out.write("".join(f"{i}\n" for i in side.indices))
+            capture_io.write_indices(indices_out, side.indices)
     return result.counts(host_frames)

@@ -36,8 +36,8 @@ from __future__ import annotations
 import dataclasses
 from typing import FrozenSet, Iterator, List, Optional, Tuple
 
-from . import replay
-from .coalesce import _spans
+from . import capture_io, replay
+from .capture_io import frame_spans
 
 KEEP_MODES = ("last", "first")
 
@@ -97,10 +97,10 @@ class Deduped:
         policy = Policy(self.keep, self.topics)
         loser, other = (self, later) if self.keep == "last" else (later, self)
         view = memoryview(other.data)
-        taken = {bytes(view[a:b]) for a, b in _spans(view) if policy.takes_part(view[a + 4])}
+        taken = {bytes(view[a:b]) for a, b in frame_spans(view) if policy.takes_part(view[a + 4])}
         view = memoryview(loser.data)
         parts, indices = [], []
-        for (a, b), i in zip(_spans(view), loser.indices):
+        for (a, b), i in zip(frame_spans(view), loser.indices):
             if not policy.takes_part(view[a + 4]) or bytes(view[a:b]) not in taken:
                 parts.append(view[a:b])
                 indices.append(i)
@@ -122,7 +122,7 @@ def dedupe_cpu(data, policy: Policy = Policy()) -> Deduped:
     ``ValueError`` for broken framing, as ``extract_cpu`` does."""
     _check_policy(policy)
     view = memoryview(data)
-    spans = list(_spans(view))
+    spans = list(frame_spans(view))
     winner = {}  # content -> the frame that is kept for it
     for i, (a, b) in enumerate(spans):
         if policy.takes_part(view[a + 4]):
@@ -152,7 +152,7 @@ def _kept(part: Deduped, policy: Policy) -> Iterator[Tuple[bytes, int, Optional[
     ``part`` brought it and Python's own hash of the bytes where it did not."""
     view = memoryview(part.data)
     hashes = None if part.hashes is None else part.hashes.tolist()
-    for k, ((a, b), i) in enumerate(zip(_spans(view), part.indices)):
+    for k, ((a, b), i) in enumerate(zip(frame_spans(view), part.indices)):
         frame = bytes(view[a:b])
         if not policy.takes_part(frame[4]):
             yield frame, i, None
@@ -260,32 +260,25 @@ def dedupe_file(path, out, policy: Policy = Policy(), device: str = "cpu",
     Returns ``{frames, kept, kept_bytes, duplicates, host_frames}``: ``duplicates`` is ``frames -
     kept``, ``host_frames`` counts the frames a device run left to the host."""
     _check_policy(policy)
-    if device == "gpu":
-        device = "cuda"
-    if device == "cpu":
-        def cut(chunk):
-            return dedupe_cpu(chunk, policy), 0
-    else:
-        from .ops import gpu_dedupe
 
-        def cut(chunk):
-            return gpu_dedupe.dedupe(chunk, policy, device=device)
+    def on_device(device):
+        from .ops import gpu_dedupe
+        return lambda chunk: gpu_dedupe.dedupe(chunk, policy, device=device)
+    cut = capture_io.per_chunk(device, lambda chunk: dedupe_cpu(chunk, policy), on_device)
     counts = {"frames": 0, "kept": 0, "kept_bytes": 0, "duplicates": 0, "host_frames": 0}
 
     def write(data: bytes, indices) -> None:
         out.write(data)
         if indices_out is not None:
-            indices_out.write("".join(f"{i}\n" for i in indices))
+            capture_io.write_indices(indices_out, indices)
         counts["kept"] += len(indices)
         counts["kept_bytes"] += len(data)
 
     first = policy.keep == "first"
     held = None   # the first chunk's result, until a second chunk arrives or the stream ends
     state = None  # _Seen under first, _KeepLast under last: built when a second chunk arrives
-    f = open(path, "rb") if isinstance(path, (str, bytes)) or hasattr(path, "__fspath__") else path
-    try:
-        for chunk in replay.iter_chunks(f, chunk_bytes):
-            part, host_frames = cut(chunk)
+    with capture_io.open_source(path) as f:
+        for _, part, host_frames in capture_io.chunk_parts(f, chunk_bytes, replay.iter_chunks, cut):
             base = counts["frames"]
             counts["frames"] += part.frames
             counts["host_frames"] += host_frames
@@ -316,9 +309,6 @@ def dedupe_file(path, out, policy: Policy = Policy(), device: str = "cpu",
                     state.add(held, 0)
                     held = None
                 state.add(part, base)
-    finally:
-        if f is not path:
-            f.close()
     if not first:
         if state is not None:
             for frame, i in state.live():

@@ -41,8 +41,9 @@ import dataclasses
 import json
 from typing import Callable, List
 
-from . import ops, replay
-from .coalesce import DROP, _spans
+from . import capture_io, ops, replay
+from .capture_io import frame_spans
+from .coalesce import DROP
 from .models import proto
 from .normalise import Policy, _check_policy
 from .topics import PROGRESS_ID, STATUS_ID, topic_name
@@ -129,7 +130,7 @@ def export_cpu(data, policy: Policy = Policy(), dialect: str = "protobufjs", bas
     _check_base(base)
     row = decoded_row_of(policy, dialect)
     view = memoryview(data)
-    spans = list(_spans(view))
+    spans = list(frame_spans(view))
     parts, indices = [], []
     events = 0
     for k, (a, b) in enumerate(spans):
@@ -169,27 +170,19 @@ def export_file(path, out, policy: Policy = Policy(), device: str = "cpu", diale
     to the host."""
     _check_policy(policy)
     replay._check_dialect(dialect)
-    if device == "gpu":
-        device = "cuda"
-    if device == "cpu":
-        def rows(chunk, base):
-            return export_cpu(chunk, policy, dialect, base), 0
-    else:
-        from .ops import gpu_export
-
-        def rows(chunk, base):
-            try:
-                return gpu_export.export(chunk, policy, device=device, dialect=dialect, base=base)
-            except gpu_export.TooLarge as e:
-                raise ValueError(f"{e}; cut smaller pieces with --chunk-bytes") from None
     counts = {"frames": 0, "rows": 0, "out_bytes": 0, "in_bytes": 0, "events": 0, "undecoded": 0, "host_frames": 0}
-    f = open(path, "rb") if isinstance(path, (str, bytes)) or hasattr(path, "__fspath__") else path
-    try:
-        for chunk in replay.iter_chunks(f, chunk_bytes):
-            part, host_frames = rows(chunk, counts["frames"])
+
+    # a chunk's rows start at the index its first frame has in the file: the frames counted so far
+    def on_device(device):
+        from .ops import gpu_export
+        return capture_io.with_chunk_bytes_hint(gpu_export.TooLarge, lambda chunk: gpu_export.export(
+            chunk, policy, device=device, dialect=dialect, base=counts["frames"]))
+    rows = capture_io.per_chunk(device, lambda chunk: export_cpu(chunk, policy, dialect, counts["frames"]), on_device)
+    with capture_io.open_source(path) as f:
+        for chunk, part, host_frames in capture_io.chunk_parts(f, chunk_bytes, replay.iter_chunks, rows):
             out.write(part.data)
             if indices_out is not None:
-                indices_out.write("".join(f"{i}\n" for i in part.indices))
+                capture_io.write_indices(indices_out, part.indices)  # absolute already
             counts["frames"] += part.frames
             counts["rows"] += len(part.indices)
             counts["out_bytes"] += len(part.data)
@@ -197,7 +190,4 @@ def export_file(path, out, policy: Policy = Policy(), device: str = "cpu", diale
             counts["events"] += part.events
             counts["undecoded"] += part.frames - part.events
             counts["host_frames"] += host_frames
-    finally:
-        if f is not path:
-            f.close()
     return counts

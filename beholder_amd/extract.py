@@ -33,7 +33,7 @@ import dataclasses
 import struct
 from typing import Callable, FrozenSet, List, Optional
 
-from . import ops, replay
+from . import capture_io, ops, replay
 from .models import proto
 from .topics import PROGRESS_ID, STATUS_ID
 
@@ -168,30 +168,19 @@ def extract_file(path, out, selector: Selector, device: str = "cpu", dialect: st
     Returns ``{frames, kept, kept_bytes, host_frames}``; ``host_frames`` counts the frames a device
     run left to the host."""
     replay._check_dialect(dialect)
-    if device == "gpu":
-        device = "cuda"
-    if device == "cpu":
-        def cut(chunk):
-            return extract_cpu(chunk, selector, dialect), 0
-    else:
-        from .ops import gpu_extract
 
-        def cut(chunk):
-            return gpu_extract.extract(chunk, selector, device=device, dialect=dialect)
+    def on_device(device):
+        from .ops import gpu_extract
+        return lambda chunk: gpu_extract.extract(chunk, selector, device=device, dialect=dialect)
+    cut = capture_io.per_chunk(device, lambda chunk: extract_cpu(chunk, selector, dialect), on_device)
     counts = {"frames": 0, "kept": 0, "kept_bytes": 0, "host_frames": 0}
-    f = open(path, "rb") if isinstance(path, (str, bytes)) or hasattr(path, "__fspath__") else path
-    try:
-        for chunk in replay.iter_chunks(f, chunk_bytes):
-            part, host_frames = cut(chunk)
+    with capture_io.open_source(path) as f:
+        for _, part, host_frames in capture_io.chunk_parts(f, chunk_bytes, replay.iter_chunks, cut):
             out.write(part.data)
-            if indices_out is not None and part.indices:
-                base = counts["frames"]
-                indices_out.write("".join(f"{base + i}\n" for i in part.indices))
+            if indices_out is not None and part.indices:  # no write call for a part that keeps nothing
+                capture_io.write_indices(indices_out, part.indices, counts["frames"])
             counts["frames"] += part.frames
             counts["kept"] += len(part.indices)
             counts["kept_bytes"] += len(part.data)
             counts["host_frames"] += host_frames
-    finally:
-        if f is not path:
-            f.close()
     return counts

@@ -49,7 +49,7 @@ import dataclasses
 import json
 from typing import Callable, List, Tuple
 
-from . import ops, replay
+from . import capture_io, ops, replay
 from .export import _check_base
 from .normalise import frame_of
 from .topics import PROGRESS_ID, STATUS_ID, TOPIC_IDS
@@ -288,28 +288,20 @@ def import_file(path, out, policy: Policy = Policy(), device: str = "cpu", chunk
     ``rows`` counts the lines that are not blank, ``host_rows`` the rows a device run left to the
     host."""
     _check_policy(policy)
-    if device == "gpu":
-        device = "cuda"
-    if device == "cpu":
-        def frames(chunk, base):
-            return import_cpu(chunk, policy, base), 0
-    else:
-        from .ops import gpu_import
-
-        def frames(chunk, base):
-            try:
-                return gpu_import.import_rows(chunk, policy, device=device, base=base)
-            except gpu_import.TooLarge as e:
-                raise ValueError(f"{e}; cut smaller pieces with --chunk-bytes") from None
     counts = {"lines": 0, "rows": 0, "frames": 0, "events": 0, "carried": 0, "skipped": 0, "blank": 0, "in_bytes": 0,
               "out_bytes": 0, "host_rows": 0}
-    f = open(path, "rb") if isinstance(path, (str, bytes)) or hasattr(path, "__fspath__") else path
-    try:
-        for chunk in iter_line_chunks(f, chunk_bytes):
-            part, host_rows = frames(chunk, counts["lines"])
+
+    # a chunk's lines are numbered from the number its first line has in the file: the lines counted so far
+    def on_device(device):
+        from .ops import gpu_import
+        return capture_io.with_chunk_bytes_hint(gpu_import.TooLarge, lambda chunk: gpu_import.import_rows(
+            chunk, policy, device=device, base=counts["lines"]))
+    frames = capture_io.per_chunk(device, lambda chunk: import_cpu(chunk, policy, counts["lines"]), on_device)
+    with capture_io.open_source(path) as f:
+        for chunk, part, host_rows in capture_io.chunk_parts(f, chunk_bytes, iter_line_chunks, frames):
             out.write(part.data)
             if lines_out is not None:
-                lines_out.write("".join(f"{i}\n" for i in part.lines))
+                capture_io.write_indices(lines_out, part.lines)  # absolute already
             rows = len(part.lines) + len(part.skipped)
             counts["lines"] += part.line_count
             counts["rows"] += rows
@@ -321,7 +313,4 @@ def import_file(path, out, policy: Policy = Policy(), device: str = "cpu", chunk
             counts["in_bytes"] += len(chunk)
             counts["out_bytes"] += len(part.data)
             counts["host_rows"] += host_rows
-    finally:
-        if f is not path:
-            f.close()
     return counts

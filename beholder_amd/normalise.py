@@ -44,8 +44,9 @@ import dataclasses
 import struct
 from typing import Callable, List
 
-from . import ops, replay
-from .coalesce import DROP, KEEP, UNDECODED_MODES, _spans
+from . import capture_io, ops, replay
+from .capture_io import frame_spans
+from .coalesce import DROP, KEEP, UNDECODED_MODES
 from .models import proto
 from .topics import PROGRESS_ID, STATUS_ID
 
@@ -121,7 +122,7 @@ def normalise_cpu(data, policy: Policy = Policy(), dialect: str = "protobufjs") 
     ``ValueError`` for broken framing, as ``extract_cpu`` does."""
     canon = canon_of(policy, dialect)
     view = memoryview(data)
-    spans = list(_spans(view))
+    spans = list(frame_spans(view))
     parts, indices = [], []
     events = rewritten = 0
     for i, (a, b) in enumerate(spans):
@@ -166,29 +167,19 @@ def normalise_file(path, out, policy: Policy = Policy(), device: str = "cpu", di
     device run left to the host."""
     _check_policy(policy)
     replay._check_dialect(dialect)
-    if device == "gpu":
-        device = "cuda"
-    if device == "cpu":
-        def cut(chunk):
-            return normalise_cpu(chunk, policy, dialect), 0
-    else:
-        from .ops import gpu_normalise
 
-        def cut(chunk):
-            try:
-                return gpu_normalise.normalise(chunk, policy, device=device, dialect=dialect)
-            except gpu_normalise.TooLarge as e:
-                raise ValueError(f"{e}; cut smaller pieces with --chunk-bytes") from None
+    def on_device(device):
+        from .ops import gpu_normalise
+        return capture_io.with_chunk_bytes_hint(gpu_normalise.TooLarge, lambda chunk: gpu_normalise.normalise(
+            chunk, policy, device=device, dialect=dialect))
+    cut = capture_io.per_chunk(device, lambda chunk: normalise_cpu(chunk, policy, dialect), on_device)
     counts = {"frames": 0, "kept": 0, "kept_bytes": 0, "in_bytes": 0, "events": 0, "rewritten": 0, "undecoded": 0,
               "host_frames": 0}
-    f = open(path, "rb") if isinstance(path, (str, bytes)) or hasattr(path, "__fspath__") else path
-    try:
-        for chunk in replay.iter_chunks(f, chunk_bytes):
-            part, host_frames = cut(chunk)
+    with capture_io.open_source(path) as f:
+        for chunk, part, host_frames in capture_io.chunk_parts(f, chunk_bytes, replay.iter_chunks, cut):
             out.write(part.data)
             if indices_out is not None:
-                base = counts["frames"]
-                indices_out.write("".join(f"{base + i}\n" for i in part.indices))
+                capture_io.write_indices(indices_out, part.indices, counts["frames"])
             counts["frames"] += part.frames
             counts["kept"] += len(part.indices)
             counts["kept_bytes"] += len(part.data)
@@ -197,7 +188,4 @@ def normalise_file(path, out, policy: Policy = Policy(), device: str = "cpu", di
             counts["rewritten"] += part.rewritten
             counts["undecoded"] += part.frames - part.events
             counts["host_frames"] += host_frames
-    finally:
-        if f is not path:
-            f.close()
     return counts

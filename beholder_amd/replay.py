@@ -33,7 +33,7 @@ import bisect
 import dataclasses
 from typing import Dict, Iterable, Iterator, Optional, Tuple
 
-from . import ops
+from . import capture_io, ops
 from .models import proto
 from .topics import PROGRESS_ID, STATUS_ID
 from .transport.framing import iter_frames
@@ -243,16 +243,20 @@ def fold_file(path, device: str = "cpu", dialect: str = "protobufjs",
     boundary and below 2^31 bytes, and merge the chunks' summaries on the host. ``device`` is
     ``cpu`` or a torch device string (``gpu`` means ``cuda``)."""
     _check_dialect(dialect)
-    if device == "gpu":
-        device = "cuda"
-    fold = (lambda chunk: fold_cpu(chunk, dialect)) if device == "cpu" else \
-        (lambda chunk: fold_gpu(chunk, device, dialect))
-    total = Summary()
-    f = open(path, "rb") if isinstance(path, (str, bytes)) or hasattr(path, "__fspath__") else path
-    try:
-        for chunk in iter_chunks(f, chunk_bytes):
-            total = total.merge(fold(chunk))
-    finally:
-        if f is not path:
-            f.close()
-    return total
+
+    def on_device(device):
+        return lambda chunk: (fold_gpu(chunk, device, dialect), 0)
+    cut = capture_io.per_chunk(device, lambda chunk: fold_cpu(chunk, dialect), on_device)
+    return merge_chunks(path, chunk_bytes, Summary(), cut)[0]
+
+
+def merge_chunks(path, chunk_bytes: int, empty, cut) -> Tuple[object, int]:
+    """What the report commands share: ``(empty merged with every chunk's part in turn, the host
+    frames' sum)`` over the file at ``path`` (or an open binary file), cut by :func:`iter_chunks`;
+    ``cut(chunk)`` gives ``(part, host_frames)``."""
+    total, host_frames = empty, 0
+    with capture_io.open_source(path) as f:
+        for _, part, on_host in capture_io.chunk_parts(f, chunk_bytes, iter_chunks, cut):
+            total = total.merge(part)
+            host_frames += on_host
+    return total, host_frames

@@ -28,8 +28,8 @@ from __future__ import annotations
 import dataclasses
 from typing import Callable, List, Optional
 
-from . import ops, replay
-from .coalesce import _spans
+from . import capture_io, ops, replay
+from .capture_io import frame_spans
 from .models import proto
 from .topics import PROGRESS_ID, STATUS_ID
 
@@ -140,7 +140,7 @@ def shard_cpu(data, policy: Policy, dialect: str = "protobufjs") -> Sharded:
     parts = [[] for _ in range(policy.shards)]
     indices = [[] for _ in range(policy.shards)]
     frame = 0
-    for frame, (a, b) in enumerate(_spans(view), 1):
+    for frame, (a, b) in enumerate(frame_spans(view), 1):
         s = route(view[a + 4], bytes(view[a + 5:b]))
         if s is DROP:
             continue
@@ -174,36 +174,25 @@ def shard_file(path, outs, policy: Policy, device: str = "cpu", dialect: str = "
     replay._check_dialect(dialect)
     if len(outs) != policy.shards or (indices_outs is not None and len(indices_outs) != policy.shards):
         raise ValueError(f"{policy.shards} shards need {policy.shards} output files")
-    if device == "gpu":
-        device = "cuda"
-    if device == "cpu":
-        def cut(chunk):
-            return shard_cpu(chunk, policy, dialect), 0
-    else:
-        from .ops import gpu_shard
 
-        def cut(chunk):
-            return gpu_shard.shard(chunk, policy, device=device, dialect=dialect)
+    def on_device(device):
+        from .ops import gpu_shard
+        return lambda chunk: gpu_shard.shard(chunk, policy, device=device, dialect=dialect)
+    cut = capture_io.per_chunk(device, lambda chunk: shard_cpu(chunk, policy, dialect), on_device)
     counts = {"frames": 0, "kept": 0, "kept_bytes": 0, "host_frames": 0,
               "per_shard": [{"frames": 0, "bytes": 0} for _ in range(policy.shards)]}
-    f = open(path, "rb") if isinstance(path, (str, bytes)) or hasattr(path, "__fspath__") else path
-    try:
-        for chunk in replay.iter_chunks(f, chunk_bytes):
-            part, host_frames = cut(chunk)
-            base = counts["frames"]
+    with capture_io.open_source(path) as f:
+        for _, part, host_frames in capture_io.chunk_parts(f, chunk_bytes, replay.iter_chunks, cut):
             for s, (data, indices) in enumerate(zip(part.data, part.indices)):
                 if not indices:
                     continue
                 outs[s].write(data)
                 if indices_outs is not None:
-                    indices_outs[s].write("".join(f"{base + i}\n" for i in indices))
+                    capture_io.write_indices(indices_outs[s], indices, counts["frames"])
                 counts["per_shard"][s]["frames"] += len(indices)
                 counts["per_shard"][s]["bytes"] += len(data)
                 counts["kept"] += len(indices)
                 counts["kept_bytes"] += len(data)
             counts["frames"] += part.frames
             counts["host_frames"] += host_frames
-    finally:
-        if f is not path:
-            f.close()
     return counts

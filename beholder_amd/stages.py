@@ -59,7 +59,7 @@ from __future__ import annotations
 import dataclasses
 from typing import Dict, Iterable, Iterator, List, Optional, Tuple
 
-from . import ops, replay
+from . import capture_io, ops, replay
 from .models import proto
 from .topics import PROGRESS_ID, STATUS_ID
 from .transitions import UNKNOWN, _class_name, class_of
@@ -373,24 +373,9 @@ def stages_file(path, device: str = "cpu", dialect: str = "protobufjs",
     ``cpu`` or a torch device string (``gpu`` means ``cuda``). Returns ``(StageReport, host_frames)``:
     the frames that a device run left to the CPU."""
     replay._check_dialect(dialect)
-    if device == "gpu":
-        device = "cuda"
-    if device == "cpu":
-        def one(chunk):
-            return stages_cpu(chunk, dialect), 0
-    else:
-        from .ops import gpu_stages
 
-        def one(chunk):
-            return gpu_stages.stages(chunk, device=device, dialect=dialect)
-    total, host_frames = StageReport(), 0
-    f = open(path, "rb") if isinstance(path, (str, bytes)) or hasattr(path, "__fspath__") else path
-    try:
-        for chunk in replay.iter_chunks(f, chunk_bytes):
-            part, on_host = one(chunk)
-            total = total.merge(part)
-            host_frames += on_host
-    finally:
-        if f is not path:
-            f.close()
-    return total, host_frames
+    def on_device(device):
+        from .ops import gpu_stages
+        return lambda chunk: gpu_stages.stages(chunk, device=device, dialect=dialect)
+    cut = capture_io.per_chunk(device, lambda chunk: stages_cpu(chunk, dialect), on_device)
+    return replay.merge_chunks(path, chunk_bytes, StageReport(), cut)

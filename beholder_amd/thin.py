@@ -37,8 +37,8 @@ from __future__ import annotations
 import dataclasses
 from typing import Callable, Dict, Iterator, List, Optional, Tuple
 
-from . import ops, replay
-from .coalesce import _spans
+from . import capture_io, ops, replay
+from .capture_io import frame_spans
 from .models import proto
 from .topics import PROGRESS_ID
 
@@ -141,7 +141,7 @@ def _marks(part: Thinned, dialect: str) -> Iterator[Tuple[bytes, int, Optional[t
     no progress event."""
     mark = mark_of(Policy(part.step, part.keep), dialect)
     view = memoryview(part.data)
-    for (a, b), i in zip(_spans(view), part.indices):
+    for (a, b), i in zip(frame_spans(view), part.indices):
         frame = bytes(view[a:b])
         yield frame, i, mark(frame[4], frame[5:])
 
@@ -151,7 +151,7 @@ def thin_cpu(data, policy: Policy = Policy(), dialect: str = "protobufjs") -> Th
     ``ValueError`` for broken framing, as ``extract_cpu`` does."""
     mark = mark_of(policy, dialect)
     view = memoryview(data)
-    spans = list(_spans(view))
+    spans = list(frame_spans(view))
     per_media: Dict[str, list] = {}  # media -> its (frame, mark) pairs in stream order
     events = 0
     for i, (a, b) in enumerate(spans):
@@ -230,32 +230,25 @@ def thin_file(path, out, policy: Policy = Policy(), device: str = "cpu", dialect
     run left to the host."""
     _check_policy(policy)
     replay._check_dialect(dialect)
-    if device == "gpu":
-        device = "cuda"
-    if device == "cpu":
-        def cut(chunk):
-            return thin_cpu(chunk, policy, dialect), 0
-    else:
-        from .ops import gpu_thin
 
-        def cut(chunk):
-            return gpu_thin.thin(chunk, policy, device=device, dialect=dialect)
+    def on_device(device):
+        from .ops import gpu_thin
+        return lambda chunk: gpu_thin.thin(chunk, policy, device=device, dialect=dialect)
+    cut = capture_io.per_chunk(device, lambda chunk: thin_cpu(chunk, policy, dialect), on_device)
     counts = {"frames": 0, "kept": 0, "kept_bytes": 0, "progress_events": 0, "dropped": 0, "host_frames": 0}
 
     def write(data: bytes, indices) -> None:
         out.write(data)
         if indices_out is not None:
-            indices_out.write("".join(f"{i}\n" for i in indices))
+            capture_io.write_indices(indices_out, indices)
         counts["kept"] += len(indices)
         counts["kept_bytes"] += len(data)
 
     first = policy.keep == "first"
     held = None   # the first chunk's result, until a second chunk arrives or the stream ends
     state = None  # media -> mark under first, _KeepLast under last: built when a second chunk arrives
-    f = open(path, "rb") if isinstance(path, (str, bytes)) or hasattr(path, "__fspath__") else path
-    try:
-        for chunk in replay.iter_chunks(f, chunk_bytes):
-            part, host_frames = cut(chunk)
+    with capture_io.open_source(path) as f:
+        for _, part, host_frames in capture_io.chunk_parts(f, chunk_bytes, replay.iter_chunks, cut):
             base = counts["frames"]
             counts["frames"] += part.frames
             counts["progress_events"] += part.progress_events
@@ -286,9 +279,6 @@ def thin_file(path, out, policy: Policy = Policy(), device: str = "cpu", dialect
                     state.add(held, 0, dialect)
                     held = None
                 state.add(part, base, dialect)
-    finally:
-        if f is not path:
-            f.close()
     if not first:
         if state is not None:
             for frame, i in state.live():

@@ -31,7 +31,7 @@ from __future__ import annotations
 import dataclasses
 from typing import Dict, Iterable, Iterator, Optional, Tuple
 
-from . import ops, replay
+from . import capture_io, ops, replay
 from .models import proto
 from .topics import STATUS_ID
 from .transport.framing import iter_frames
@@ -248,24 +248,9 @@ def transitions_file(path, device: str = "cpu", dialect: str = "protobufjs",
     is ``cpu`` or a torch device string (``gpu`` means ``cuda``). Returns ``(Transitions,
     host_frames)``: the frames that a device run left to the host."""
     replay._check_dialect(dialect)
-    if device == "gpu":
-        device = "cuda"
-    if device == "cpu":
-        def one(chunk):
-            return transitions_cpu(chunk, dialect), 0
-    else:
-        from .ops import gpu_transitions
 
-        def one(chunk):
-            return gpu_transitions.transitions(chunk, device=device, dialect=dialect)
-    total, host_frames = Transitions(), 0
-    f = open(path, "rb") if isinstance(path, (str, bytes)) or hasattr(path, "__fspath__") else path
-    try:
-        for chunk in replay.iter_chunks(f, chunk_bytes):
-            part, on_host = one(chunk)
-            total = total.merge(part)
-            host_frames += on_host
-    finally:
-        if f is not path:
-            f.close()
-    return total, host_frames
+    def on_device(device):
+        from .ops import gpu_transitions
+        return lambda chunk: gpu_transitions.transitions(chunk, device=device, dialect=dialect)
+    cut = capture_io.per_chunk(device, lambda chunk: transitions_cpu(chunk, dialect), on_device)
+    return replay.merge_chunks(path, chunk_bytes, Transitions(), cut)
