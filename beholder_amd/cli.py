@@ -13,6 +13,7 @@ transitions  count a framed stream's per-media status moves: the transition matr
 hosts    what every worker host did in a framed stream: events, media, stints, handovers, what it held (``hosts``).
 stages   join both topics of a framed stream per media: what stage each is in and how far (``stages``).
 extract  cut a framed stream down to selected frames, a framed stream again (``extract``).
+recover  salvage the frames of a damaged framed stream: cut out the spans that fit no frame, a framed stream again (``recover``).
 normalise  rewrite every decodable event of a framed stream in its canonical encoding, a framed stream again (``normalise``).
 anonymise  replace every mediaId and host of a framed stream by a keyed pseudonym, a framed stream again (``anonymise``).
 dedupe   drop the byte-identical repeat frames of a framed stream, a framed stream again (``dedupe``).
@@ -25,7 +26,8 @@ bench    run the BASELINE.json measurement configs (see ``beholder_amd.bench.har
 publish  publish a framed stream to an AMQP broker.
 
 Exit codes: 0 ok, 1 runtime failure, 2 usage/config error (startup failures are
-fatal — the documented fix of quirk Q10); ``compare --exit-code`` adds 3, the captures differ.
+fatal — the documented fix of quirk Q10); ``compare --exit-code`` adds 3, the captures differ, and
+``recover --exit-code`` adds 3, the capture was not intact.
 """
 from __future__ import annotations
 
@@ -527,6 +529,25 @@ def cmd_normalise(a: argparse.Namespace) -> int:
         source, out, policy, device=a.device, dialect=a.dialect, chunk_bytes=a.chunk_bytes, indices_out=indices))
 
 
+def cmd_recover(a: argparse.Namespace) -> int:
+    """Salvage the frames of a damaged framed stream (``beholder_amd.recover``)."""
+    from . import recover
+    try:
+        policy = recover.Policy(max_frame=a.max_frame)
+    except ValueError as e:
+        print(f"beholder: {e}", file=sys.stderr)
+        return 2
+    if not _gpu_ready(a, "gpu_recover"):
+        return 1
+    source, out, offsets = _lazy_outputs(a, a.offsets)
+    gaps = _LazyOutput(a.gaps, text=True) if a.gaps else None
+    intact = []
+    status = _rewrite((out, offsets, gaps), lambda: recover.recover_file(
+        source, out, policy, device=a.device, dialect=a.dialect, chunk_bytes=a.chunk_bytes, gaps_out=gaps,
+        offsets_out=offsets), warn=lambda counts: intact.append(counts["intact"]))
+    return 3 if a.exit_code and intact == [False] else status
+
+
 ANONYMISE_KEY_ENV = "BEHOLDER_ANONYMISE_KEY"
 
 
@@ -906,6 +927,23 @@ def build_parser() -> argparse.ArgumentParser:
     _capture_args(h, "shard", CUT_HELP)
     _indices_arg(h, "write each shard's input indices to these files, one per line; '{}' as in -o", metavar="PATTERN")
     h.set_defaults(fn=cmd_shard)
+
+    v = sub.add_parser("recover", help="damaged framed stream -> its frames, with the spans that fit no frame cut out",
+                       description="Walk the framing; where a header does not fit, skip to the next offset "
+                                   "where a status or progress frame with a mediaId starts and is followed by "
+                                   "another frame or the end, and go on from there. The frame just before a "
+                                   "gap is the one to distrust. The counts go to stderr as one JSON line.")
+    v.add_argument("-o", "--out", required=True, help="output file ('-': stdout)")
+    v.add_argument("--gaps", metavar="FILE",
+                   help="write one NDJSON row per gap here: offset, length, and after_frame, the output index of "
+                        "the frame before it or -1")
+    v.add_argument("--offsets", metavar="FILE", help="write the recovered frames' input offsets here, one per line")
+    v.add_argument("--max-frame", type=int, default=1 << 20, metavar="N",
+                   help="the longest frame length a header may hold, 1 to 16777216; --chunk-bytes is at least "
+                        "four times this and 16")
+    v.add_argument("--exit-code", action="store_true", help="exit with status 3 where the capture was not intact")
+    _capture_args(v, "recover", READ_HELP)
+    v.set_defaults(fn=cmd_recover)
 
     m = sub.add_parser("compare", help="two framed streams -> what is only in one, what is in both, in what order",
                        description="Match A and B as multisets of frames: the k-th occurrence of a content (topic "

@@ -3,7 +3,8 @@ loaded, and what its callers share: the launch helper, the argument checks and t
 overflow list (``ops/gpu_decode.py``, ``ops/gpu_fold.py``, ``ops/gpu_extract.py``,
 ``ops/gpu_coalesce.py``, ``ops/gpu_shard.py``, ``ops/gpu_dedupe.py``, ``ops/gpu_transitions.py``,
 ``ops/gpu_thin.py``, ``ops/gpu_hosts.py``, ``ops/gpu_stages.py``, ``ops/gpu_normalise.py``,
-``ops/gpu_compare.py``, ``ops/gpu_export.py``, ``ops/gpu_anonymise.py``, ``ops/gpu_import.py``).
+``ops/gpu_compare.py``, ``ops/gpu_export.py``, ``ops/gpu_anonymise.py``, ``ops/gpu_import.py``,
+``ops/gpu_recover.py``).
 
 The library is built in-tree by ``beholder_amd._build.build_hip`` (hipcc, gfx950) and loaded with
 ctypes after ``import torch``. torch's HIP runtime has the same soname, so the kernels launch on
@@ -118,6 +119,17 @@ def lib() -> ctypes.CDLL:
         so.bh_import_classify.restype = i
         so.bh_import_emit.argtypes = [p, i] + [p] * 4
         so.bh_import_emit.restype = i
+        # telemetry_recover.hip (ops/gpu_recover.py): candidates, next, reach, mark, resolve
+        so.bh_recover_candidates.argtypes = [p, ctypes.c_longlong, i, i, i, i] + [p] * 5
+        so.bh_recover_candidates.restype = i
+        so.bh_recover_next.argtypes = [p, p, i, i] + [p] * 5
+        so.bh_recover_next.restype = i
+        so.bh_recover_reach.argtypes = [p] * 4 + [i, i, p]
+        so.bh_recover_reach.restype = i
+        so.bh_recover_mark.argtypes = [p, i, i, p, p]
+        so.bh_recover_mark.restype = i
+        so.bh_recover_resolve.argtypes = [p, i] + [p] * 5
+        so.bh_recover_resolve.restype = i
         _lib = so
     return _lib
 
