@@ -2,8 +2,9 @@
 (``ops/hip/telemetry_anonymise.hip``): the device path of ``python -m beholder_amd anonymise --device
 gpu`` (:mod:`beholder_amd.anonymise` defines the result).
 
-The stages are the normalise's (``ops/gpu_normalise.py``), which ``scripts/gpu_anonymise_probe.py``
-times one by one next to them:
+The stages are the normalise's (``ops/gpu_normalise.py``), over the tables and host stages that the
+rewriting commands share (``ops/gpu_rewrite.py``); ``scripts/gpu_anonymise_probe.py`` times them one
+by one next to the normalise's:
 
 1. ``gpu_fold.index`` and ``gpu_fold.upload`` — as for the fold.
 2. :func:`classify` — one lane per frame reads the frame as the normalise does, hashes the chosen
@@ -11,7 +12,8 @@ times one by one next to them:
    the host: the key does not go to the device) and stores its plan and the length of its output
    frame. A frame the device does not write (the normalise's rule, or a chosen string above 4,096
    bytes) goes to the overflow list with length 0.
-3. :func:`decide_on_host` — the normalise's, with ``anonymise.anon_of`` in place of ``canon_of``.
+3. :func:`decide_on_host` — ``gpu_rewrite.decide_with``, as the normalise's, with ``anonymise.anon_of``
+   in place of ``canon_of``.
 4. ``gpu_extract.scan`` and ``totals`` — the extract's prefix sum, as it is, over ``keep_len``.
 5. :func:`emit` — a wave per 64 frames writes the planned frames' bytes at their offsets; a digit of
    a pseudonym comes from the plan's digest words. It writes nothing into the spans of host frames.
@@ -23,12 +25,11 @@ behind :func:`anonymise`.
 """
 from __future__ import annotations
 
-from typing import NamedTuple
-
 import numpy as np
 
-from . import gpu_extract, gpu_fold, gpu_normalise, hip_lib
-from .gpu_normalise import LIMIT, HostFrames, TooLarge, collect  # noqa: F401  collect: stage 6, as it is
+from . import gpu_extract, gpu_fold, gpu_normalise, gpu_rewrite, hip_lib
+from .gpu_normalise import TooLarge, collect  # noqa: F401  collect: stage 6, as it is
+from .gpu_rewrite import LIMIT, HostParts, Tables  # noqa: F401  the shared shapes, under the names the callers know
 
 C_EVENTS, C_ERRORS, C_OTHER, C_OVERFLOW, N_COUNTERS = 0, 1, 2, 3, 4  # counters[] of the kernels
 PLAN_FIELDS = gpu_normalise.PLAN_FIELDS + tuple(f"{s}_digest{k}" for s in ("id", "host") for k in range(4))
@@ -37,25 +38,11 @@ AN_GROWTH_MAX = 72    # telemetry_anonymise.hpp, with its derivation
 AN_STRING_MAX = 4096  # a longer chosen string goes to the host
 
 
-class Tables(NamedTuple):
-    """The device tensors of one anonymise, in the shape of the normalise's; ``select`` holds the
-    extract's over ``keep_len``, for its scan."""
-    n: int
-    buf: object
-    offs: object
-    plans: object     # (n, 16) int32: PLAN_FIELDS
-    keep_len: object  # n int32: the output frame's length, 0 for a dropped frame
-    counters: object  # N_COUNTERS int32
-    overflow: object  # n int32
-    select: gpu_extract.ScanTables
-
-
 def _check_policy(policy) -> None:
     from .. import anonymise
     if not isinstance(policy, anonymise.Policy):
         raise TypeError(f"policy is an anonymise.Policy, not {type(policy).__name__}")
-    if policy.undecoded not in ("keep", "drop"):
-        raise ValueError("undecoded is keep or drop")
+    gpu_rewrite.check_undecoded(policy)
     if not policy.fields or not set(policy.fields) <= set(FIELD_BITS):
         raise ValueError("fields is a non-empty subset of mediaId and host")
     if not isinstance(policy.key, bytes) or not 16 <= len(policy.key) <= 32:
@@ -73,15 +60,8 @@ def check_size(size: int, n: int, extra: int = 0) -> None:
 def allocate(buf_dev, offs_dev, n: int) -> Tables:
     """Tables for ``n`` frames next to ``buf_dev``, zeroed where the kernels need it. Checks the
     arguments on the host."""
-    import torch
-    hip_lib.check_stream(buf_dev, offs_dev, n, "the anonymise")
-    check_size(buf_dev.numel(), n)
-    dev = buf_dev.device
-    keep_len = torch.empty(n, dtype=torch.int32, device=dev)
-    return Tables(n, buf_dev, offs_dev, torch.empty((n, len(PLAN_FIELDS)), dtype=torch.int32, device=dev), keep_len,
-                  torch.zeros(N_COUNTERS, dtype=torch.int32, device=dev),
-                  torch.empty(n, dtype=torch.int32, device=dev),
-                  gpu_extract.scan_tables(keep_len, n, buf_dev, offs_dev))
+    return gpu_rewrite.allocate(buf_dev, offs_dev, n, len(PLAN_FIELDS), N_COUNTERS, "the anonymise",
+                                lambda: check_size(buf_dev.numel(), n))
 
 
 def classify(t: Tables, policy, dialect: str = "protobufjs") -> None:
@@ -96,26 +76,22 @@ def classify(t: Tables, policy, dialect: str = "protobufjs") -> None:
                  t.keep_len.data_ptr(), t.counters.data_ptr(), t.overflow.data_ptr())
 
 
-def decide_on_host(t: Tables, data, offs: np.ndarray, policy, dialect: str = "protobufjs") -> HostFrames:
+def decide_on_host(t: Tables, data, offs: np.ndarray, policy, dialect: str = "protobufjs") -> HostParts:
     """Reads the overflow list's length; where it is not 0, asks ``anonymise.anon_of`` about those
     frames and writes the lengths of their output frames into ``t.keep_len``. Raises
     :class:`TooLarge` where they grow the output past what the scan's 32 bits hold."""
     from .. import anonymise
-    return gpu_normalise.decide_with(t, data, offs, lambda: anonymise.anon_of(policy, dialect), check_size)
+    return gpu_rewrite.decide_with(t, C_OVERFLOW, data, offs, lambda: anonymise.anon_of(policy, dialect), check_size)
 
 
 def emit(t: Tables, kept: int, kept_bytes: int):
     """The output in a new device buffer of exactly ``kept_bytes``, the host frames' spans left as
     they are. ``kept`` and ``kept_bytes`` must be the totals of the scan over ``t.keep_len``: the
     kernel trusts them. No frame in the output launches nothing."""
-    import torch
-    if not (0 <= kept <= t.n and 0 <= kept_bytes < LIMIT and (kept == 0) == (kept_bytes == 0)):
-        raise ValueError("kept and kept_bytes are the scan's totals")
-    out = torch.empty(kept_bytes, dtype=torch.uint8, device=t.buf.device)
-    if kept == 0:
-        return out
-    hip_lib.call("bh_anonymise_emit", t.buf, t.buf.data_ptr(), t.n, t.plans.data_ptr(), t.select.pos.data_ptr(),
-                 out.data_ptr())
+    out = gpu_rewrite.emit_out(t, kept, kept_bytes)
+    if kept:
+        hip_lib.call("bh_anonymise_emit", t.buf, t.buf.data_ptr(), t.n, t.plans.data_ptr(), t.select.pos.data_ptr(),
+                     out.data_ptr())
     return out
 
 

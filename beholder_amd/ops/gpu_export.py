@@ -22,59 +22,34 @@ The stages, which ``scripts/gpu_export_probe.py`` times one by one:
 7. :func:`collect` — the output and the indices come back, and the host splices its rows into their
    spans.
 
+The tables, the scatter, the emit's front and :func:`collect` are the rewriting commands' own
+(``ops/gpu_rewrite.py``), shared with the normalise, the anonymise and the import.
+
 The extension is loaded by ``ops/hip_lib.py``. A missing library raises; there is no CPU fallback
 behind :func:`export`.
 """
 from __future__ import annotations
 
-from typing import List, NamedTuple, Tuple
-
 import numpy as np
 
-from . import gpu_extract, gpu_fold, hip_lib
+from . import gpu_extract, gpu_fold, gpu_rewrite, hip_lib
+from .gpu_rewrite import LIMIT, HostParts, Tables, collect  # noqa: F401  collect: stage 7, as it is
 
 C_EVENTS, C_ERRORS, C_OTHER, C_TOO_LONG, C_OVERFLOW, N_COUNTERS = 0, 1, 2, 3, 4, 5  # counters[] of the kernels
 EX_B64, EX_DROP, EX_HOST, EX_STATUS, EX_PROGRESS, EX_TOO_LONG = 0, 1, 2, 3, 4, 5  # RowPlan::kind of telemetry_export.hpp
 PLAN_FIELDS = ("id_off", "id_len", "status", "progress", "host_off", "host_len", "id_esc", "host_esc", "kind", "topic",
                "row_len", "reserved")
-LIMIT = 2 ** 31  # the scan keeps bytes in 32 bits and out_offs in int32
 
 
 class TooLarge(ValueError):
     """The rows of the stream do not stay below 2^31 bytes."""
 
 
-class Tables(NamedTuple):
-    """The device tensors of one export; ``select`` holds the extract's over ``keep_len``, for its
-    scan."""
-    n: int
-    base: int         # the index of frame 0 in the whole input
-    buf: object
-    offs: object
-    plans: object     # (n, 12) int32: PLAN_FIELDS
-    keep_len: object  # n int32: the row's length, 0 for a dropped frame
-    counters: object  # N_COUNTERS int32
-    overflow: object  # n int32
-    select: gpu_extract.ScanTables
-
-
-class HostFrames(NamedTuple):
-    """What :func:`decide_on_host` keeps for :func:`collect`."""
-    count: int          # the overflow list's length
-    frames: np.ndarray  # the frames among them with a row, ascending
-    parts: List[bytes]  # their rows
-    events: int         # the decoded events among the list
-
-
-NO_HOST_FRAMES = HostFrames(0, np.zeros(0, dtype=np.int64), [], 0)
-
-
 def _check_policy(policy) -> None:
     from .. import export
     if not isinstance(policy, export.Policy):
         raise TypeError(f"policy is an export.Policy, not {type(policy).__name__}")
-    if policy.undecoded not in ("keep", "drop"):
-        raise ValueError("undecoded is keep or drop")
+    gpu_rewrite.check_undecoded(policy)
 
 
 def _check_base(base) -> None:
@@ -89,14 +64,8 @@ def _too_large(size: int) -> TooLarge:
 def allocate(buf_dev, offs_dev, n: int, base: int = 0) -> Tables:
     """Tables for ``n`` frames next to ``buf_dev``, zeroed where the kernels need it. Checks the
     arguments on the host."""
-    import torch
-    hip_lib.check_stream(buf_dev, offs_dev, n, "the export")
-    _check_base(base)
-    dev = buf_dev.device
-    keep_len = torch.empty(n, dtype=torch.int32, device=dev)
-    return Tables(n, base, buf_dev, offs_dev, torch.empty((n, len(PLAN_FIELDS)), dtype=torch.int32, device=dev),
-                  keep_len, torch.zeros(N_COUNTERS, dtype=torch.int32, device=dev),
-                  torch.empty(n, dtype=torch.int32, device=dev), gpu_extract.scan_tables(keep_len, n, buf_dev, offs_dev))
+    return gpu_rewrite.allocate(buf_dev, offs_dev, n, len(PLAN_FIELDS), N_COUNTERS, "the export",
+                                lambda: _check_base(base), base)
 
 
 def classify(t: Tables, policy, dialect: str = "protobufjs") -> None:
@@ -109,12 +78,10 @@ def classify(t: Tables, policy, dialect: str = "protobufjs") -> None:
                  t.counters.data_ptr(), t.overflow.data_ptr())
 
 
-def decide_on_host(t: Tables, data, offs: np.ndarray, policy, dialect: str = "protobufjs") -> HostFrames:
+def decide_on_host(t: Tables, data, offs: np.ndarray, policy, dialect: str = "protobufjs") -> HostParts:
     """Reads the counters. :class:`TooLarge` where one row alone reaches 2^31 bytes. Where the
     overflow list is not empty, asks ``export.decoded_row_of`` about those frames and writes the
     lengths of their rows into ``t.keep_len``."""
-    import torch
-
     from .. import export
     from ..coalesce import DROP
     counters = t.counters.cpu().numpy().tolist()
@@ -122,7 +89,7 @@ def decide_on_host(t: Tables, data, offs: np.ndarray, policy, dialect: str = "pr
         raise _too_large(LIMIT)
     count = counters[C_OVERFLOW]
     if count == 0:
-        return NO_HOST_FRAMES
+        return gpu_rewrite.NO_HOST_PARTS
     row = export.decoded_row_of(policy, dialect)
     where, parts = [], []
     events = 0
@@ -135,12 +102,7 @@ def decide_on_host(t: Tables, data, offs: np.ndarray, policy, dialect: str = "pr
             raise _too_large(len(r))
         where.append(i)
         parts.append(r)
-    frames = np.asarray(where, dtype=np.int64)
-    if where:
-        dev = t.buf.device
-        lengths = np.fromiter(map(len, parts), dtype=np.int32, count=len(parts))
-        t.keep_len[torch.from_numpy(frames).to(dev)] = torch.from_numpy(lengths).to(dev)
-    return HostFrames(count, frames, parts, events)
+    return HostParts(count, gpu_rewrite.scatter(t, where, parts), parts, events)
 
 
 def keep_len_sum(t: Tables) -> int:
@@ -163,28 +125,11 @@ def emit(t: Tables, kept: int, kept_bytes: int):
     """The output in a new device buffer of exactly ``kept_bytes``, the host rows' spans left as they
     are. ``kept`` and ``kept_bytes`` must be the totals of the scan over ``t.keep_len``: the kernel
     trusts them. No row in the output launches nothing."""
-    import torch
-    if not (0 <= kept <= t.n and 0 <= kept_bytes < LIMIT and (kept == 0) == (kept_bytes == 0)):
-        raise ValueError("kept and kept_bytes are the scan's totals")
-    out = torch.empty(kept_bytes, dtype=torch.uint8, device=t.buf.device)
-    if kept == 0:
-        return out
-    hip_lib.call("bh_export_emit", t.buf, t.buf.data_ptr(), t.n, t.base, t.plans.data_ptr(), t.select.pos.data_ptr(),
-                 out.data_ptr())
+    out = gpu_rewrite.emit_out(t, kept, kept_bytes)
+    if kept:
+        hip_lib.call("bh_export_emit", t.buf, t.buf.data_ptr(), t.n, t.base, t.plans.data_ptr(),
+                     t.select.pos.data_ptr(), out.data_ptr())
     return out
-
-
-def collect(t: Tables, out, kept: int, host: HostFrames) -> Tuple[bytes, List[int]]:
-    """The rows and their indices in the whole input, on the host, with the host's rows spliced into
-    their spans."""
-    import torch
-    stream = out.cpu().numpy()
-    if host.parts:
-        at = (t.select.pos[torch.from_numpy(host.frames).to(out.device)] & 0xFFFFFFFF).cpu().numpy().tolist()
-        for start, row in zip(at, host.parts):
-            stream[start:start + len(row)] = np.frombuffer(row, dtype=np.uint8)
-    indices = t.select.indices[:kept].cpu().numpy().astype(np.int64)
-    return stream.tobytes(), (indices + t.base).tolist()
 
 
 def export(data, policy, device="cuda", dialect: str = "protobufjs", base: int = 0):

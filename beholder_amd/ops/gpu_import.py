@@ -26,16 +26,18 @@ The stages, which ``scripts/gpu_import_probe.py`` times one by one:
 7. :func:`collect` — the output and the line positions come back, and the host splices its frames
    into their spans.
 
+The tables, the scatter, the emit's front and :func:`collect` are the rewriting commands' own
+(``ops/gpu_rewrite.py``), shared with the normalise, the anonymise and the export.
+
 The extension is loaded by ``ops/hip_lib.py``. A missing library raises; there is no CPU fallback
 behind :func:`import_rows`.
 """
 from __future__ import annotations
 
-from typing import List, NamedTuple, Tuple
+from typing import NamedTuple
 
-import numpy as np
-
-from . import gpu_extract, hip_lib
+from . import gpu_extract, gpu_rewrite, hip_lib
+from .gpu_rewrite import HostParts, Tables, collect  # noqa: F401  collect: stage 7, as it is, over the lines
 
 C_EVENTS, C_CARRIED, C_BLANK, C_OVERFLOW, N_COUNTERS = 0, 1, 2, 3, 4  # counters[] of the kernels
 IM_BLANK, IM_B64, IM_STATUS, IM_PROGRESS, IM_HOST = 0, 1, 2, 3, 4  # FramePlan::kind of telemetry_import.hpp
@@ -53,32 +55,6 @@ class Lines(NamedTuple):
     """What :func:`split` found."""
     n: int          # the lines
     starts: object  # n + 1 int32 on the device: line m is buf[starts[m], starts[m + 1] - 1)
-
-
-class Tables(NamedTuple):
-    """The device tensors of one import; ``select`` holds the extract's over ``keep_len``, for its
-    scan."""
-    n: int
-    buf: object
-    offs: object      # the line starts
-    plans: object     # (n, 12) int32: PLAN_FIELDS
-    keep_len: object  # n int32: the frame's length, 0 for a line without one
-    counters: object  # N_COUNTERS int32
-    overflow: object  # n int32
-    select: gpu_extract.ScanTables
-
-
-class HostRows(NamedTuple):
-    """What :func:`decide_on_host` keeps for :func:`collect`."""
-    count: int          # the overflow list's length
-    lines: np.ndarray   # the lines among them with a frame, ascending
-    parts: List[bytes]  # their frames
-    events: int         # the frames among them from json rows
-    carried: int        # the frames among them from b64 rows
-    skipped: List[int]  # the malformed lines among them, ascending, as positions in the chunk
-
-
-NO_HOST_ROWS = HostRows(0, np.zeros(0, dtype=np.int64), [], 0, 0, [])
 
 
 def _check_policy(policy) -> None:
@@ -145,16 +121,10 @@ def split(buf_dev) -> Lines:
 
 
 def allocate(buf_dev, starts_dev, n: int) -> Tables:
-    """Tables for ``n`` lines next to ``buf_dev``, zeroed where the kernels need it. Checks the
-    arguments on the host."""
-    import torch
+    """Tables for ``n`` lines next to ``buf_dev``, the line starts in the place of ``offs``, zeroed
+    where the kernels need it. Checks the arguments on the host."""
     _check_text(buf_dev)
-    hip_lib.check_stream(buf_dev, starts_dev, n, "the import")
-    dev = buf_dev.device
-    keep_len = torch.empty(n, dtype=torch.int32, device=dev)
-    return Tables(n, buf_dev, starts_dev, torch.empty((n, len(PLAN_FIELDS)), dtype=torch.int32, device=dev), keep_len,
-                  torch.zeros(N_COUNTERS, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
-                  gpu_extract.scan_tables(keep_len, n, buf_dev, starts_dev))
+    return gpu_rewrite.allocate(buf_dev, starts_dev, n, len(PLAN_FIELDS), N_COUNTERS, "the import")
 
 
 def classify(t: Tables) -> None:
@@ -164,7 +134,7 @@ def classify(t: Tables) -> None:
                  t.keep_len.data_ptr(), t.counters.data_ptr(), t.overflow.data_ptr())
 
 
-def decide_on_host(t: Tables, data, policy, base: int = 0) -> HostRows:
+def decide_on_host(t: Tables, data, policy, base: int = 0) -> HostParts:
     """Reads the counters. Where the overflow list is not empty, asks ``import_rows.frame_of_row``
     about those lines in ascending order and writes the lengths of their frames into ``t.keep_len``.
     Under ``fail`` the first malformed line raises ``ValueError`` with its number, ``base`` plus its
@@ -175,8 +145,7 @@ def decide_on_host(t: Tables, data, policy, base: int = 0) -> HostRows:
     _check_policy(policy)
     count = int(t.counters[C_OVERFLOW].item())
     if count == 0:
-        return NO_HOST_ROWS
-    dev = t.buf.device
+        return gpu_rewrite.NO_HOST_PARTS
     rows = torch.sort(t.overflow[:count].to(torch.int64)).values
     spans = torch.stack((t.offs[rows], t.offs[rows + 1])).cpu().numpy()  # only these lines' starts come back
     frame = definition.decided_frame_of_row(policy)
@@ -196,38 +165,18 @@ def decide_on_host(t: Tables, data, policy, base: int = 0) -> HostRows:
         parts.append(f)
         carried += from_b64
         events += not from_b64
-    lines = np.asarray(where, dtype=np.int64)
-    if where:
-        lengths = np.fromiter(map(len, parts), dtype=np.int32, count=len(parts))
-        t.keep_len[torch.from_numpy(lines).to(dev)] = torch.from_numpy(lengths).to(dev)
-    return HostRows(count, lines, parts, events, carried, skipped)
+    return HostParts(count, gpu_rewrite.scatter(t, where, parts), parts, events, carried=carried, skipped=skipped)
 
 
 def emit(t: Tables, kept: int, kept_bytes: int):
     """The output in a new device buffer of exactly ``kept_bytes``, the host frames' spans left as
     they are. ``kept`` and ``kept_bytes`` must be the totals of the scan over ``t.keep_len``: the
     kernel trusts them. No frame in the output launches nothing."""
-    import torch
-    if not (0 <= kept <= t.n and 0 <= kept_bytes < t.buf.numel() and (kept == 0) == (kept_bytes == 0)):
-        raise ValueError("kept and kept_bytes are the scan's totals")
-    out = torch.empty(kept_bytes, dtype=torch.uint8, device=t.buf.device)
-    if kept == 0:
-        return out
-    hip_lib.call("bh_import_emit", t.buf, t.buf.data_ptr(), t.n, t.plans.data_ptr(), t.select.pos.data_ptr(),
-                 out.data_ptr())
+    out = gpu_rewrite.emit_out(t, kept, kept_bytes, t.buf.numel())  # the frames are shorter than their rows
+    if kept:
+        hip_lib.call("bh_import_emit", t.buf, t.buf.data_ptr(), t.n, t.plans.data_ptr(), t.select.pos.data_ptr(),
+                     out.data_ptr())
     return out
-
-
-def collect(t: Tables, out, kept: int, host: HostRows) -> Tuple[bytes, List[int]]:
-    """The frames and their lines' positions in the chunk, on the host, with the host's frames
-    spliced into their spans."""
-    import torch
-    stream = out.cpu().numpy()
-    if host.parts:
-        at = (t.select.pos[torch.from_numpy(host.lines).to(out.device)] & 0xFFFFFFFF).cpu().numpy().tolist()
-        for start, f in zip(at, host.parts):
-            stream[start:start + len(f)] = np.frombuffer(f, dtype=np.uint8)
-    return stream.tobytes(), t.select.indices[:kept].cpu().numpy().astype(np.int64).tolist()
 
 
 def import_rows(data, policy, device="cuda", base: int = 0):

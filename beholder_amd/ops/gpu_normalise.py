@@ -21,59 +21,36 @@ The stages, which ``scripts/gpu_normalise_probe.py`` times one by one:
 6. :func:`collect` — the output and the indices come back, and the host splices its frames' bytes
    into their spans.
 
+The tables, the scatter, the emit's front and the splice are the rewriting commands' own
+(``ops/gpu_rewrite.py``), shared with the anonymise, the export and the import.
+
 The extension is loaded by ``ops/hip_lib.py``. A missing library raises; there is no CPU fallback
 behind :func:`normalise`.
 """
 from __future__ import annotations
 
-from typing import List, NamedTuple, Tuple
+from typing import List, Tuple
 
 import numpy as np
 
-from . import gpu_extract, gpu_fold, hip_lib
+from . import gpu_extract, gpu_fold, gpu_rewrite, hip_lib
+from .gpu_rewrite import LIMIT, HostParts, Tables  # noqa: F401  the shared shapes, under the names the callers know
 
 C_EVENTS, C_ERRORS, C_OTHER, C_OVERFLOW, C_REWRITTEN, N_COUNTERS = 0, 1, 2, 3, 4, 5  # counters[] of the kernels
 NM_COPY, NM_DROP, NM_HOST, NM_STATUS, NM_PROGRESS = 0, 1, 2, 3, 4  # Plan::kind of telemetry_normalise.hpp
 PLAN_FIELDS = ("id_off", "id_len", "status", "progress", "host_off", "host_len", "kind", "out_len")
 NM_GROWTH_MAX = 10  # telemetry_normalise.hpp, with its derivation
-LIMIT = 2 ** 31     # the scan keeps bytes in 32 bits and out_offs in int32
 
 
 class TooLarge(ValueError):
     """The stream, grown by what normalising can add, does not stay below 2^31 bytes."""
 
 
-class Tables(NamedTuple):
-    """The device tensors of one normalise; ``select`` holds the extract's over ``keep_len``, for
-    its scan."""
-    n: int
-    buf: object
-    offs: object
-    plans: object     # (n, 8) int32: PLAN_FIELDS
-    keep_len: object  # n int32: the output frame's length, 0 for a dropped frame
-    counters: object  # N_COUNTERS int32
-    overflow: object  # n int32
-    select: gpu_extract.ScanTables
-
-
-class HostFrames(NamedTuple):
-    """What :func:`decide_on_host` keeps for :func:`collect`."""
-    count: int         # the overflow list's length
-    frames: np.ndarray  # the frames among them with an output frame, ascending
-    parts: List[bytes]  # their output frames
-    events: int        # the decoded events among the list
-    rewritten: int     # and those whose bytes changed
-
-
-NO_HOST_FRAMES = HostFrames(0, np.zeros(0, dtype=np.int64), [], 0, 0)
-
-
 def _check_policy(policy) -> None:
     from .. import normalise
     if not isinstance(policy, normalise.Policy):
         raise TypeError(f"policy is a normalise.Policy, not {type(policy).__name__}")
-    if policy.undecoded not in ("keep", "drop"):
-        raise ValueError("undecoded is keep or drop")
+    gpu_rewrite.check_undecoded(policy)
 
 
 def check_size(size: int, n: int, extra: int = 0) -> None:
@@ -87,14 +64,8 @@ def check_size(size: int, n: int, extra: int = 0) -> None:
 def allocate(buf_dev, offs_dev, n: int) -> Tables:
     """Tables for ``n`` frames next to ``buf_dev``, zeroed where the kernels need it. Checks the
     arguments on the host."""
-    import torch
-    hip_lib.check_stream(buf_dev, offs_dev, n, "the normalise")
-    check_size(buf_dev.numel(), n)
-    dev = buf_dev.device
-    keep_len = torch.empty(n, dtype=torch.int32, device=dev)
-    return Tables(n, buf_dev, offs_dev, torch.empty((n, len(PLAN_FIELDS)), dtype=torch.int32, device=dev), keep_len,
-                  torch.zeros(N_COUNTERS, dtype=torch.int32, device=dev),
-                  torch.empty(n, dtype=torch.int32, device=dev), gpu_extract.scan_tables(keep_len, n, buf_dev, offs_dev))
+    return gpu_rewrite.allocate(buf_dev, offs_dev, n, len(PLAN_FIELDS), N_COUNTERS, "the normalise",
+                                lambda: check_size(buf_dev.numel(), n))
 
 
 def classify(t: Tables, policy, dialect: str = "protobufjs") -> None:
@@ -107,75 +78,31 @@ def classify(t: Tables, policy, dialect: str = "protobufjs") -> None:
                  t.overflow.data_ptr())
 
 
-def decide_on_host(t: Tables, data, offs: np.ndarray, policy, dialect: str = "protobufjs") -> HostFrames:
+def decide_on_host(t: Tables, data, offs: np.ndarray, policy, dialect: str = "protobufjs") -> HostParts:
     """Reads the overflow list's length; where it is not 0, asks ``normalise.canon_of`` about those
     frames and writes the lengths of their output frames into ``t.keep_len``. Raises
     :class:`TooLarge` where they grow the output past what the scan's 32 bits hold."""
     from .. import normalise
-    return decide_with(t, data, offs, lambda: normalise.canon_of(policy, dialect), check_size)
-
-
-def decide_with(t, data, offs: np.ndarray, make_canon, check) -> HostFrames:
-    """:func:`decide_on_host` for any tables of this shape (``ops/gpu_anonymise.py`` has its own):
-    ``make_canon()`` gives the per-frame function, made only where the list is not empty, and
-    ``check(size, n, extra)`` is the caller's size check."""
-    import torch
-
-    from .. import normalise
-    from ..coalesce import DROP, KEEP
-    count = int(t.counters[C_OVERFLOW].item())
-    if count == 0:
-        return NO_HOST_FRAMES
-    canon = make_canon()
-    where, parts = [], []
-    events = rewritten = growth = 0
-    for i, topic, body in hip_lib.overflow_frames(t.overflow, count, data, offs)[1]:
-        c = canon(topic, body)
-        if c is DROP:
-            continue
-        if c is not KEEP:
-            events += 1
-            rewritten += c != body
-            body = c
-        frame = normalise.frame_of(topic, body)
-        growth += max(0, len(frame) - (int(offs[i + 1]) - int(offs[i])))
-        where.append(i)
-        parts.append(frame)
-    check(t.buf.numel(), t.n, growth)
-    frames = np.asarray(where, dtype=np.int64)
-    if where:
-        dev = t.buf.device
-        lengths = np.fromiter(map(len, parts), dtype=np.int32, count=len(parts))
-        t.keep_len[torch.from_numpy(frames).to(dev)] = torch.from_numpy(lengths).to(dev)
-    return HostFrames(count, frames, parts, events, rewritten)
+    return gpu_rewrite.decide_with(t, C_OVERFLOW, data, offs, lambda: normalise.canon_of(policy, dialect), check_size)
 
 
 def emit(t: Tables, kept: int, kept_bytes: int):
     """The output in a new device buffer of exactly ``kept_bytes``, the host frames' spans left as
     they are. ``kept`` and ``kept_bytes`` must be the totals of the scan over ``t.keep_len``: the
     kernel trusts them. No frame in the output launches nothing."""
-    import torch
-    if not (0 <= kept <= t.n and 0 <= kept_bytes < LIMIT and (kept == 0) == (kept_bytes == 0)):
-        raise ValueError("kept and kept_bytes are the scan's totals")
-    out = torch.empty(kept_bytes, dtype=torch.uint8, device=t.buf.device)
-    if kept == 0:
-        return out
-    hip_lib.call("bh_normalise_emit", t.buf, t.buf.data_ptr(), t.offs.data_ptr(), t.n, t.plans.data_ptr(),
-                 t.select.pos.data_ptr(), out.data_ptr(), t.counters.data_ptr())
+    out = gpu_rewrite.emit_out(t, kept, kept_bytes)
+    if kept:
+        hip_lib.call("bh_normalise_emit", t.buf, t.buf.data_ptr(), t.offs.data_ptr(), t.n, t.plans.data_ptr(),
+                     t.select.pos.data_ptr(), out.data_ptr(), t.counters.data_ptr())
     return out
 
 
-def collect(t: Tables, out, kept: int, host: HostFrames) -> Tuple[bytes, List[int]]:
+def collect(t: Tables, out, kept: int, host: HostParts) -> Tuple[bytes, List[int]]:
     """The output stream and its frames' input indices, on the host, with the host's frames spliced
     into their spans: ``gpu_extract.collect`` where there are none."""
     if not host.parts:
         return gpu_extract.collect(t.select, out, kept)
-    import torch
-    stream = out.cpu().numpy()
-    at = (t.select.pos[torch.from_numpy(host.frames).to(out.device)] & 0xFFFFFFFF).cpu().numpy().tolist()
-    for start, frame in zip(at, host.parts):
-        stream[start:start + len(frame)] = np.frombuffer(frame, dtype=np.uint8)
-    return stream.tobytes(), t.select.indices[:kept].cpu().numpy().tolist()
+    return gpu_rewrite.collect(t, out, kept, host)
 
 
 def normalise(data, policy, device="cuda", dialect: str = "protobufjs"):

@@ -30,7 +30,9 @@
 // counts); every plain load reads what an earlier launch or the host wrote. No kernel waits for
 // another workgroup. Every lane's loops are bounded by the frame's own length, and the hash's by
 // 4,096 bytes.
+#include "launch_grid.hpp"
 #include "telemetry_anonymise.hpp"
+#include "wave_lane.hpp"
 
 namespace {
 
@@ -67,12 +69,6 @@ __global__ __launch_bounds__(BLOCK) void an_classify(const uint8_t* __restrict__
   if (threadIdx.x < 3 && local[threadIdx.x]) atomicAdd(&counters[threadIdx.x], local[threadIdx.x]);
 }
 
-// x of lane i, i the same in every lane: a scalar.
-__device__ __forceinline__ int32_t from_lane(int32_t x, int i) { return __builtin_amdgcn_readlane(x, i); }
-__device__ __forceinline__ uint32_t from_lane(uint32_t x, int i) {
-  return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int32_t>(x), i));
-}
-
 // One wave per 64 frames; pos[m] & 0xffffffff is frame m's output byte offset.
 __global__ __launch_bounds__(BLOCK) void an_emit(const uint8_t* __restrict__ buf, const AnonPlan* __restrict__ plans,
                                                  const uint64_t* __restrict__ pos, int n, uint8_t* __restrict__ out) {
@@ -107,8 +103,6 @@ __global__ __launch_bounds__(BLOCK) void an_emit(const uint8_t* __restrict__ buf
     for (int b = lane; b < L; b += 64) out[d + b] = static_cast<uint8_t>(anon_byte(buf, plan, b));
   }
 }
-
-int blocks_of(long long count, int per_block) { return static_cast<int>((count + per_block - 1) / per_block); }
 
 }  // namespace
 

@@ -37,6 +37,7 @@
 // Visibility is media_table.hpp's rule: within a launch workgroups meet only in atomics (the cursor,
 // the counts); every plain load reads what an earlier launch or the host wrote. No kernel waits for
 // another workgroup. The one loop over bytes, the hash, is bounded by DEDUPE_DEVICE_MAX.
+#include "launch_grid.hpp"
 #include "telemetry_compare.hpp"
 
 namespace {
@@ -143,8 +144,6 @@ __global__ __launch_bounds__(BLOCK) void cmp_breaks(const int32_t* __restrict__ 
   __syncthreads();
   if (threadIdx.x == 0 && sum) atomicAdd(&counters[C_BREAKS], sum);
 }
-
-int blocks_of(long long count, int per_block) { return static_cast<int>((count + per_block - 1) / per_block); }
 
 }  // namespace
 

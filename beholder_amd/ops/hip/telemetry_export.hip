@@ -28,7 +28,9 @@
 // Visibility is the fold's rule: within a launch workgroups meet only in atomics (the cursor, the
 // counts); every plain load reads what an earlier launch or the host wrote. No kernel waits for
 // another workgroup. Every lane's loops are bounded by the frame's own length.
+#include "launch_grid.hpp"
 #include "telemetry_export.hpp"
+#include "wave_lane.hpp"
 
 namespace {
 
@@ -62,9 +64,6 @@ __global__ __launch_bounds__(BLOCK) void ex_classify(const uint8_t* __restrict__
   __syncthreads();
   if (threadIdx.x < 4 && local[threadIdx.x]) atomicAdd(&counters[threadIdx.x], local[threadIdx.x]);
 }
-
-// x of lane i, i the same in every lane: a scalar.
-__device__ __forceinline__ int32_t from_lane(int32_t x, int i) { return __builtin_amdgcn_readlane(x, i); }
 
 // Bytes [from, to) of the row in hand to out + d, lane b taking from + b, from + b + 64, ...
 __device__ __forceinline__ void plain_bytes(const uint8_t* __restrict__ buf, const RowPlan& plan, uint64_t index,
@@ -137,8 +136,6 @@ __global__ __launch_bounds__(BLOCK) void ex_emit(const uint8_t* __restrict__ buf
     plain_bytes(buf, plan, index, out, d, at, plan.row_len, lane);
   }
 }
-
-int blocks_of(long long count, int per_block) { return static_cast<int>((count + per_block - 1) / per_block); }
 
 }  // namespace
 

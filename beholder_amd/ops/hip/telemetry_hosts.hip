@@ -52,6 +52,7 @@
 // the cursor, the counts); every plain load reads what an earlier launch or the host wrote, which is
 // why number is a launch of its own before pairs. No kernel waits for another workgroup. Every
 // lane's loops are bounded by the frame's own length or by the table's size.
+#include "launch_grid.hpp"
 #include "telemetry_hosts.hpp"
 
 namespace {
@@ -181,8 +182,6 @@ __global__ __launch_bounds__(BLOCK) void ho_walk(const uint32_t* __restrict__ ke
   for (uint32_t k = threadIdx.x; k < held; k += BLOCK)
     if (table[k]) atomicAdd(&worker_rows[k], table[k]);
 }
-
-int blocks_of(long long count, int per_block) { return static_cast<int>((count + per_block - 1) / per_block); }
 
 bool table_size(long long slots, long long least) {
   return slots >= least && slots <= (1ll << 30) && (slots & (slots - 1)) == 0;

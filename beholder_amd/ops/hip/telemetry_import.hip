@@ -34,7 +34,9 @@
 // counts); every plain load reads what an earlier launch or the host wrote. No kernel waits for
 // another workgroup. Every lane's loops are bounded by the line's own length.
 #include "block_scan.hpp"
+#include "launch_grid.hpp"
 #include "telemetry_import.hpp"
+#include "wave_lane.hpp"
 
 namespace {
 
@@ -95,9 +97,6 @@ __global__ __launch_bounds__(BLOCK) void im_classify(const uint8_t* __restrict__
   __syncthreads();
   if (threadIdx.x < 3 && local[threadIdx.x]) atomicAdd(&counters[threadIdx.x], local[threadIdx.x]);
 }
-
-// x of lane i, i the same in every lane: a scalar.
-__device__ __forceinline__ int32_t from_lane(int32_t x, int i) { return __builtin_amdgcn_readlane(x, i); }
 
 // Bytes [from, to) of the frame in hand to out + d, lane b taking from + b, from + b + 64, ...
 __device__ __forceinline__ void plain_bytes(const uint8_t* __restrict__ buf, const FramePlan& plan,
@@ -163,8 +162,6 @@ __global__ __launch_bounds__(BLOCK) void im_emit(const uint8_t* __restrict__ buf
     plain_bytes(buf, plan, out, d, at, plan.out_len, lane);
   }
 }
-
-int blocks_of(long long count, int per_block) { return static_cast<int>((count + per_block - 1) / per_block); }
 
 constexpr long long SIZE_LIMIT = 1ll << 31;  // starts are int32
 

@@ -29,7 +29,9 @@
 // Visibility is the fold's rule: within a launch workgroups meet only in atomics (the cursor, the
 // counts); every plain load reads what an earlier launch or the host wrote. No kernel waits for
 // another workgroup. Every lane's loops are bounded by the frame's own length.
+#include "launch_grid.hpp"
 #include "telemetry_normalise.hpp"
+#include "wave_lane.hpp"
 
 namespace {
 
@@ -65,9 +67,6 @@ __global__ __launch_bounds__(BLOCK) void nm_classify(const uint8_t* __restrict__
   __syncthreads();
   if (threadIdx.x < 3 && local[threadIdx.x]) atomicAdd(&counters[threadIdx.x], local[threadIdx.x]);
 }
-
-// x of lane i, i the same in every lane: a scalar.
-__device__ __forceinline__ int32_t from_lane(int32_t x, int i) { return __builtin_amdgcn_readlane(x, i); }
 
 // One wave per 64 frames; pos[m] & 0xffffffff is frame m's output byte offset.
 __global__ __launch_bounds__(BLOCK) void nm_emit(const uint8_t* __restrict__ buf, const int32_t* __restrict__ offs,
@@ -112,8 +111,6 @@ __global__ __launch_bounds__(BLOCK) void nm_emit(const uint8_t* __restrict__ buf
   }
   if (lane == 0 && rewritten) atomicAdd(&counters[C_REWRITTEN], rewritten);
 }
-
-int blocks_of(long long count, int per_block) { return static_cast<int>((count + per_block - 1) / per_block); }
 
 }  // namespace
 

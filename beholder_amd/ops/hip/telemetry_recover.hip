@@ -37,6 +37,7 @@
 // cursor) and in the reach bytes, where every store is the same 1; every other plain load reads what
 // an earlier launch or the host wrote. No kernel waits for another workgroup.
 #include "block_min_scan.hpp"
+#include "launch_grid.hpp"
 #include "telemetry_recover.hpp"
 
 namespace {
@@ -147,8 +148,6 @@ __global__ __launch_bounds__(BLOCK) void rc_resolve(const int32_t* __restrict__ 
   framed[k] = wf ? 1 : 0;
 }
 
-int blocks_of(long long count) { return static_cast<int>((count + BLOCK - 1) / BLOCK); }
-
 bool sized(int n, int decided) { return n >= 1 && n <= RC_LIMIT && decided >= 0 && decided <= n; }
 
 }  // namespace
@@ -170,7 +169,7 @@ extern "C" __attribute__((visibility("default"))) int bh_recover_candidates(
   if (n <= 0) return 0;
   if (!sized(n, decided) || (dialect != DIALECT_UPB && dialect != DIALECT_PROTOBUFJS) || max_frame < 1 ||
       max_frame > (16 << 20) || !buf || (reinterpret_cast<uintptr_t>(buf) & 15) != 0 ||
-      padded < static_cast<long long>(blocks_of(n)) * BLOCK + 16 || !flags || !end || !cursor || !overflow)
+      padded < static_cast<long long>(blocks_of(n, BLOCK)) * BLOCK + 16 || !flags || !end || !cursor || !overflow)
     return static_cast<int>(hipErrorInvalidValue);
   auto st = static_cast<hipStream_t>(stream);
   const auto* b = static_cast<const uint8_t*>(buf);
@@ -179,11 +178,11 @@ extern "C" __attribute__((visibility("default"))) int bh_recover_candidates(
   auto* c = static_cast<uint32_t*>(cursor);
   auto* o = static_cast<int32_t*>(overflow);
   if (dialect == DIALECT_PROTOBUFJS)
-    hipLaunchKernelGGL(rc_candidates<DIALECT_PROTOBUFJS>, dim3(blocks_of(n)), dim3(BLOCK), 0, st, b, n, decided,
+    hipLaunchKernelGGL(rc_candidates<DIALECT_PROTOBUFJS>, dim3(blocks_of(n, BLOCK)), dim3(BLOCK), 0, st, b, n, decided,
                        max_frame, f, e, c, o);
   else
-    hipLaunchKernelGGL(rc_candidates<DIALECT_UPB>, dim3(blocks_of(n)), dim3(BLOCK), 0, st, b, n, decided, max_frame, f,
-                       e, c, o);
+    hipLaunchKernelGGL(rc_candidates<DIALECT_UPB>, dim3(blocks_of(n, BLOCK)), dim3(BLOCK), 0, st, b, n, decided,
+                       max_frame, f, e, c, o);
   return static_cast<int>(hipGetLastError());
 }
 
@@ -197,7 +196,7 @@ extern "C" __attribute__((visibility("default"))) int bh_recover_next(
   if (n <= 0) return 0;
   if (!sized(n, decided) || !flags || !end || !mins || !sfx || !next || !succ)
     return static_cast<int>(hipErrorInvalidValue);
-  const int blocks = blocks_of(static_cast<long long>(n) + 1);
+  const int blocks = blocks_of(static_cast<long long>(n) + 1, BLOCK);
   auto st = static_cast<hipStream_t>(stream);
   const auto* f = static_cast<const uint8_t*>(flags);
   auto* mn = static_cast<int32_t*>(mins);
@@ -229,7 +228,7 @@ extern "C" __attribute__((visibility("default"))) int bh_recover_reach(
   auto* out = static_cast<int32_t*>(spare);
   hipLaunchKernelGGL(rc_reach_init, dim3(1), dim3(1), 0, st, static_cast<const int32_t*>(next), resync, r);
   hipError_t err = hipGetLastError();
-  const int grid = blocks_of(static_cast<long long>(n) + 1);
+  const int grid = blocks_of(static_cast<long long>(n) + 1, BLOCK);
   for (int round = doubling_rounds(n); round > 0 && err == hipSuccess; --round) {
     hipLaunchKernelGGL(rc_reach_round, dim3(grid), dim3(BLOCK), 0, st, in, out, r, n);
     err = hipGetLastError();
@@ -245,7 +244,7 @@ extern "C" __attribute__((visibility("default"))) int bh_recover_mark(const void
                                                                       void* keep_len, void* stream) {
   if (n <= 0) return 0;
   if (!sized(n, decided) || !reach || !keep_len) return static_cast<int>(hipErrorInvalidValue);
-  hipLaunchKernelGGL(rc_mark, dim3(blocks_of(n)), dim3(BLOCK), 0, static_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(rc_mark, dim3(blocks_of(n, BLOCK)), dim3(BLOCK), 0, static_cast<hipStream_t>(stream),
                      static_cast<const uint8_t*>(reach), n, decided, static_cast<int32_t*>(keep_len));
   return static_cast<int>(hipGetLastError());
 }
@@ -257,7 +256,7 @@ extern "C" __attribute__((visibility("default"))) int bh_recover_resolve(
   if (count <= 0) return 0;
   if (count > RC_LIMIT || !nodes || !flags || !next || !frame_at || !framed)
     return static_cast<int>(hipErrorInvalidValue);
-  hipLaunchKernelGGL(rc_resolve, dim3(blocks_of(count)), dim3(BLOCK), 0, static_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(rc_resolve, dim3(blocks_of(count, BLOCK)), dim3(BLOCK), 0, static_cast<hipStream_t>(stream),
                      static_cast<const int32_t*>(nodes), count, static_cast<const uint8_t*>(flags),
                      static_cast<const int32_t*>(next), static_cast<int32_t*>(frame_at), static_cast<uint8_t*>(framed));
   return static_cast<int>(hipGetLastError());

@@ -53,6 +53,7 @@
 // load reads what an earlier launch or the host wrote, which is why the carry is three launches and
 // not a single look-back pass. No kernel waits for another workgroup. All sums and maxima are of
 // integers: the result is exact and the same from run to run.
+#include "launch_grid.hpp"
 #include "telemetry_stages.hpp"
 
 namespace {
@@ -250,8 +251,6 @@ __global__ __launch_bounds__(BLOCK) void st_settle(const uint32_t* __restrict__ 
   for (uint32_t k = threadIdx.x; k < T_WORDS; k += BLOCK)
     if (cells[k]) atomicAdd(&tables[k], cells[k]);
 }
-
-int blocks_of(long long count, int per_block) { return static_cast<int>((count + per_block - 1) / per_block); }
 
 }  // namespace
 

@@ -32,6 +32,7 @@
 // Visibility is the fold's rule: within a launch workgroups meet only in atomics (the cursor, the
 // counts); every plain load reads what an earlier launch or the host wrote. No kernel waits for
 // another workgroup. Every lane's loops are bounded by the frame's own length.
+#include "launch_grid.hpp"
 #include "telemetry_thin.hpp"
 
 namespace {
@@ -89,8 +90,6 @@ __global__ __launch_bounds__(BLOCK) void th_mark(const uint32_t* __restrict__ ke
   const unsigned long long dropped = __ballot(drop);  // every lane of the wave is here: no lane left early
   if ((threadIdx.x & 63) == 0 && dropped) atomicAdd(&counters[C_DROPPED], static_cast<uint32_t>(__popcll(dropped)));
 }
-
-int blocks_of(long long count, int per_block) { return static_cast<int>((count + per_block - 1) / per_block); }
 
 }  // namespace
 

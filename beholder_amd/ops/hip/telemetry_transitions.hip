@@ -49,6 +49,7 @@
 // Visibility is media_table.hpp's rule. Every lane's loops are bounded by the frame's own length or
 // by the table's size.
 #include "block_scan.hpp"
+#include "launch_grid.hpp"
 #include "telemetry_transitions.hpp"
 
 namespace {
@@ -256,8 +257,6 @@ __global__ __launch_bounds__(BLOCK) void tr_pairs(const uint32_t* __restrict__ k
   for (int k = threadIdx.x; k < static_cast<int>(CLASSES * CLASSES); k += BLOCK)
     if (cells[k]) atomicAdd(&matrix[k], cells[k]);
 }
-
-int blocks_of(long long count, int per_block) { return static_cast<int>((count + per_block - 1) / per_block); }
 
 }  // namespace
 

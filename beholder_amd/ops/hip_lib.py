@@ -4,7 +4,7 @@ overflow list (``ops/gpu_decode.py``, ``ops/gpu_fold.py``, ``ops/gpu_extract.py`
 ``ops/gpu_coalesce.py``, ``ops/gpu_shard.py``, ``ops/gpu_dedupe.py``, ``ops/gpu_transitions.py``,
 ``ops/gpu_thin.py``, ``ops/gpu_hosts.py``, ``ops/gpu_stages.py``, ``ops/gpu_normalise.py``,
 ``ops/gpu_compare.py``, ``ops/gpu_export.py``, ``ops/gpu_anonymise.py``, ``ops/gpu_import.py``,
-``ops/gpu_recover.py``).
+``ops/gpu_recover.py``, and ``ops/gpu_rewrite.py`` for what the rewriting four of them share).
 
 The library is built in-tree by ``beholder_amd._build.build_hip`` (hipcc, gfx950) and loaded with
 ctypes after ``import torch``. torch's HIP runtime has the same soname, so the kernels launch on
